@@ -28,10 +28,14 @@ the max time over ranks are RCCL all-reduces too (rl_comm_allreduce_f64).
 RLAMD_COLLECTIVE=torch swaps in a torch all_reduce of the merge buffer (a
 rehearsal mode for ranks sharing one GPU, where RCCL cannot run; it imports torch).
 
-Prints ONE JSON line on rank 0.  `roofline` names the dominant kernel's binding
-ceiling from the PMC counters of this very build (profiles/counters.json, matched
-by rl_build_id), see roofline(); `cpu_baseline` times C restatements of the
-reference loop on the host cores (bounded samples).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps,
+writes --dump-outputs if asked and prints the line; `roofline` in it is arithmetic
+on the timed steps' own figures: the dominant kernel's binding ceiling from the PMC
+counters of this very build (profiles/counters.json, matched by rl_build_id), see
+roofline().  --full adds what takes work of its own after the timed steps:
+`q_check`, the merged Q's digest against the committed oracle answers, and
+`cpu_baseline`, C restatements of the reference loop timed on the host cores
+(bounded samples; --no-cpu-baseline leaves it out).
 """
 import argparse
 import hashlib
@@ -81,8 +85,14 @@ def parse():
     ap.add_argument("--timing-every", type=int, default=None,
                     help="HIP events around every N-th timed launch (the kernel's average duration; 0: none); "
                          "default 8, 1 for the private rows (a 100-ms launch hides the events' cost)")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline sample budget")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the merged-Q "
+                         "digest against the committed fixtures (q_check) and the CPU baseline (cpu_baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step left a caller as DIR/<name>.npy "
+                         "(dump_outputs)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: CPU baseline sample budget")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--counters-file", default=os.path.join(ROOT, "profiles", "counters.json"),
                     help="PMC summaries per workload (scripts/collect_counters.py)")
     a = ap.parse_args()
@@ -257,6 +267,45 @@ def private_q_check(args, agent):
     return {"lanes": [L - PRIV_WINDOW, L], "q_sha256": qh, "w_sha256": wh, "launches": args.warmup + args.steps,
             "fixture": fx[0] if fx else None,
             "match": (fx[1]["q_sha256"] == qh and fx[1].get("w_sha256") == wh) if fx else None}
+
+
+DUMP_LANES = 1 << 16
+
+
+def dump_outputs(args, agent, out_dir):
+    """--dump-outputs DIR: what the last timed step left a caller of the timed path
+    (rl_agent_run), as float64 .npy files, so that two builds run with the same
+    arguments can be compared output for output (env lanes are seeded by global lane
+    id: the inputs of a run are a function of its arguments alone).
+      q.npy            shared mode: the merged Q table [P][S][A] (rl_agent_get_q)
+      q_lanes.npy      private agents: Q of the last min(L, 4096) lanes [n][P][S][A]
+      weights_lanes.npy  NeuralPolicy: the same lanes' network parameters [n][n_par]
+      lane_state.npy   core + aux words (rl_agent_lane_state) of min(L, 2^16) lanes drawn
+                       without replacement by numpy's default_rng(0), ascending [n][8]
+      lane_ids.npy     those lanes' ids
+      stats.npy        rl_agent_stats, in the order of rlamd.Stats' fields
+    Rank 0 writes (its own lanes); at most 8 MB at 2^16 lanes + the tables."""
+    import numpy as np
+    import rlamd
+    os.makedirs(out_dir, exist_ok=True)
+    L = args.lanes
+
+    def save(name, x):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(x, np.float64))
+
+    if args.group != 1:
+        save("q", agent.q())
+    else:
+        n = min(L, PRIV_WINDOW)
+        save("q_lanes", agent.q_lanes(L - n, n))
+        if args.policy == "neural":
+            save("weights_lanes", agent.weights_lanes(L - n, n))
+    ids = np.sort(np.random.default_rng(0).choice(L, min(L, DUMP_LANES), replace=False))
+    core, aux = agent.lane_state()
+    save("lane_state", np.concatenate([core[ids], aux[ids]], axis=1))
+    save("lane_ids", ids)
+    st = agent.stats()
+    save("stats", [st[k] for k, _ in rlamd.Stats._fields_])
 
 
 def counters_for(args, build_id):
@@ -654,8 +703,11 @@ def main():
     # the merged Q after the run (untimed): SHA-256 of its raw int64 words, every
     # rank's digest compared, and the committed one-process answer for this global
     # lane set when there is one (a self-checking N-rank run)
+    # (--full: a plain run leaves `q_check` null)
     q_check = None
-    if args.group != 1:
+    if not args.full:
+        pass
+    elif args.group != 1:
         qh = hashlib.sha256(agent.q_raw().astype("<i8").tobytes()).hexdigest()
         agree = True
         if comm is not None:              # 48 bits of the digest are exact in an f64
@@ -715,7 +767,9 @@ def main():
                                                        "events on the agent's stream (rl_agent_get_timing) around "
                                                        f"every {args.timing_every}-th timed launch"},
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args, agent, args.dump_outputs)
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args)
     if rank == 0:
         print(json.dumps(out), flush=True)

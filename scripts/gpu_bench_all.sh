@@ -10,7 +10,7 @@ run() {   # key, bench args
 import json; d=json.load(open('gpurun_out/bench_$1.json')); r=d['roofline']
 print('$1', '%.4g'%d['value'], 'kern_ms %.4f'%r['kernel_avg_ms'], 'frac %.3f'%r['frac'], 'issue', r.get('issue_frac'), 'clamp', d.get('q_clamp_hits'))"
 }
-run cfg2 ""
+run cfg2 "--full"
 run cfg2_slippery "--config 2 --slippery 1 --no-cpu-baseline"
 run cfg3 "--config 3 --no-cpu-baseline"
 run cfg4 "--config 4 --no-cpu-baseline"

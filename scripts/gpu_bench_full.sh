@@ -2,6 +2,7 @@
 # full bench lines (cpu_baseline included) for the given SURVEY cfgs -> gpurun_out/bench_cfg<c>.json
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
+BENCH_ARGS="--full ${BENCH_ARGS}"
 for c in ${CONFIGS:-2 3 4 5}; do
   timeout -k 10 300 python -u bench.py --config $c ${BENCH_ARGS} > gpurun_out/bench_cfg$c.log 2>&1 || { rc=$?; tail -5 gpurun_out/bench_cfg$c.log; exit $rc; }
   grep '^{' gpurun_out/bench_cfg$c.log | tail -1 > gpurun_out/bench_cfg$c.json

@@ -16,12 +16,12 @@ import json; d=json.load(open('gpurun_out/bench_$1.json')); r=d['roofline']; c=d
 print('$1', '%.4g'%d['value'], 'kern_ms %.4f'%r['kernel_avg_ms'], 'bound', r['bound'], 'cpu', c.get('value'))"
 }
 if [ -z "$SKIP_BENCH" ]; then
-  bench cfg2 ""
-  bench cfg2_slippery "--config 2 --slippery 1"
-  bench cfg3 "--config 3"
-  bench cfg4 "--config 4"
-  bench cfg4_2p19 "--config 4 --lanes 524288 --no-cpu-baseline"
-  bench cfg5 "--config 5"
+  bench cfg2 "--full"
+  bench cfg2_slippery "--full --config 2 --slippery 1"
+  bench cfg3 "--full --config 3"
+  bench cfg4 "--full --config 4"
+  bench cfg4_2p19 "--full --config 4 --lanes 524288 --no-cpu-baseline"
+  bench cfg5 "--full --config 5"
 fi
 if [ -z "$SKIP_PROF" ]; then
   for spec in ${PROF:-2:0:cfg2 2:1:cfg2_slippery 3:0:cfg3 4:0:cfg4 5:0:cfg5}; do

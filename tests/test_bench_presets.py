@@ -39,6 +39,14 @@ def test_presets(monkeypatch, cfg, env, policy, lanes, group):
         assert (a.selector, a.algo) == ("ucb", "qlearning")
 
 
+def test_plain_run_is_the_default(monkeypatch):
+    """--full (q_check, cpu_baseline) and --dump-outputs are off unless asked for"""
+    a = _parse(monkeypatch, "--gpus", "1", "--steps", "7", "--warmup", "2")
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    a = _parse(monkeypatch, "--full", "--dump-outputs", "d")
+    assert a.full is True and a.dump_outputs == "d"
+
+
 def test_workload_keys_distinct(monkeypatch):
     import bench
     keys = set()

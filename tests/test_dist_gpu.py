@@ -150,7 +150,8 @@ def test_bench_two_ranks_q_check_matches_one_process(extra, fixture, scaling):
     every rank holds the same digest and it equals the oracle's for that set
     (tests/golden/global_q.json) — weak (--lanes: 2 x 2^20 lanes) and the
     default at N > 1, the metric's fixed 2^20 lanes split over the ranks (strong)"""
-    r = _torchrun(["bench.py", "--gpus", "2", "--steps", "20", "--warmup", "5", "--no-cpu-baseline"] + extra)
+    r = _torchrun(["bench.py", "--gpus", "2", "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline"]
+                  + extra)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     d = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")][-1]
     qc = d["q_check"]
@@ -167,7 +168,7 @@ def test_bench_gpus2_self_launch_strong_default():
     env = dict(os.environ, RLAMD_DIST_BACKEND="gloo", RLAMD_COLLECTIVE="torch")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "20", "--warmup", "5",
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "20", "--warmup", "5", "--full",
                         "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
@@ -195,8 +196,8 @@ def test_bench_gpus2_peer_merge_q_check(config, fixture, n):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, "bench.py", "--config", str(config), "--gpus", str(n), "--steps", "20",
-                        "--warmup", "5", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True,
-                       timeout=300)
+                        "--warmup", "5", "--full", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True,
+                       text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     d = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")][-1]
     qc = d["q_check"]
@@ -215,7 +216,7 @@ def test_bench_rccl_peer_setup_one_rank():
     env.pop("RLAMD_COLLECTIVE", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--steps", "20",
-           "--warmup", "5", "--no-cpu-baseline"]
+           "--warmup", "5", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     d = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")][-1]

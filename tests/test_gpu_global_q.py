@@ -47,7 +47,7 @@ def test_bench_q_check_matches_fixture(rl):
     cfg2_L1M_25, the case every --lanes-total 1048576 run shares)"""
     import subprocess
     root = os.path.dirname(HERE)
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "5",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "5", "--full",
                           "--no-cpu-baseline"], check=True, capture_output=True, text=True, timeout=300).stdout
     d = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
     qc = d["q_check"]
