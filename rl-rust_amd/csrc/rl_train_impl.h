@@ -1363,7 +1363,14 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
                     if constexpr (RLAMD_RM_PIN) asm volatile("" : "+v"(rarg), "+v"(rmaxd));
                 } else {
                     double v[A];
-                    qd_row(s2, v);
+                    if (BJC && !bj_nonterminal(s2)) {
+                        // a terminal row has no LDS row and no f64 image (bj_row of it lies
+                        // past the compact rows): the words load_rows read from Q_base
+#pragma unroll
+                        for (int i = 0; i < A; ++i) v[i] = q_val(ra2[i]);
+                    } else {
+                        qd_row(s2, v);
+                    }
                     rarg = (int32_t)argmax_max_f64<A>(v, rmaxd);
                     if constexpr (RLAMD_FUSE_MAX == 2) asm volatile("" : "+v"(rarg), "+v"(rmaxd));
                 }

@@ -198,6 +198,9 @@ SHARED_CASES = [
     # compact Blackjack LDS rows (eps-greedy): terminal rows read from Q_base —
     # q_default != 0 makes them matter for the TD target and the argmax
     dict(env="blackjack", algo="sarsa", group_size=300, q_default=0.25),
+    # the same under the fixed point's f64 images (single-table Q-learning): the
+    # target row's max at a terminal s' comes from Q_base too
+    dict(env="blackjack", algo="qlearning", group_size=512, q_default=0.25),
     dict(env="blackjack", agent="traces", policy="double", algo="expected_sarsa", group_size=128,
          q_default=-0.5),
     dict(env="blackjack", selector="ucb", algo="qlearning", group_size=64),      # dense rows (UCB)

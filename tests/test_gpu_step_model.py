@@ -1,0 +1,80 @@
+"""The device's shared-Q step combine and launch merge against the exact replay
+model (tests/step_model.py): the cases, tables and helper of
+tests/test_step_model.py, driven on rl.Agent instead of the CPU oracle.
+
+Every launch is replayed from the device's own rl_step_record entries: the
+model's raw Q words and UCB counters must equal the device's, every td
+recomputed from the group's step-start snapshot must equal the recorded one,
+and the coverage conditions must hold on the device's records.  No oracle call
+is made here, so a mistake shared by the oracle and the kernels cannot hide.
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from test_step_model import (CASES, COMMON, HEADROOM_CASE, ONE_LANE, assert_coverage, crafted_table,
+                             one_lane_plain_update, replay_and_check, setup_pair)
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_device_equals_replay_model(rl, name):
+    kw, opt = CASES[name]
+    p = rl.default_params(**COMMON, **kw)
+    dev = rl.Agent(p)
+    try:
+        setup_pair(dev, p, opt, (dev.P, dev.S, dev.A))
+        met = replay_and_check(dev, p, lambda: dev.run(1))
+        assert_coverage(met, opt["need"])
+        if opt.get("table", ("", 0))[0] == "d":
+            want = crafted_table(*opt["table"], dev.P, dev.S, dev.A)
+            assert np.array_equal(dev.q(), want), "a move too small to change an entry changed the merged table"
+    finally:
+        dev.close()
+
+
+def test_device_headroom_equals_replay_model(rl):
+    """4096 declared learner groups (2 headroom bits) through the external-collective
+    path: caller-owned merge buffer, launch_train / launch_fold / launch_apply; one
+    rank, so the collectives are the identity"""
+    kw, opt = HEADROOM_CASE
+    p = rl.default_params(**COMMON, **kw)
+    # device memory from the HIP runtime librlamd itself is linked to
+    hip = C.CDLL("libamdhip64.so")
+    dev = rl.Agent(p)
+    buf = C.c_void_p()
+    try:
+        setup_pair(dev, p, opt, (dev.P, dev.S, dev.A))
+        cap = dev.delta_cap_words()
+        assert cap >= dev.delta_words()
+        assert hip.hipMalloc(C.byref(buf), C.c_size_t(cap * 8)) == 0
+        assert hip.hipMemset(buf, 0, C.c_size_t(cap * 8)) == 0
+        dev.set_delta_buffer(buf.value, cap)
+        dev.set_merge_groups(opt["merge_groups"])
+
+        def launch():
+            dev.launch_train()
+            dev.launch_fold()
+            dev.launch_apply()
+            dev.synchronize()
+
+        met = replay_and_check(dev, p, launch, merge_groups=opt["merge_groups"])
+        assert_coverage(met, opt["need"])
+    finally:
+        dev.close()
+        if buf.value:
+            hip.hipFree(buf)
+
+
+@pytest.mark.parametrize("name", list(ONE_LANE))
+def test_device_one_lane_is_plain_update(rl, name):
+    p = rl.default_params(n_lanes=1, group_size=2, **COMMON, **ONE_LANE[name])
+    dev = rl.Agent(p)
+    try:
+        dev.set_q_mode("f64")
+        dev.set_recording(True)
+        one_lane_plain_update(dev, p)
+    finally:
+        dev.close()
