@@ -110,7 +110,8 @@ enum rl_q_mode {        /* rl_agent_set_q_mode */
  * TaxiEnv::new(max_steps) (taxi.rs:57), BlackJackEnv::new() (blackjack.rs:32). */
 typedef struct rl_env_config {
     int32_t kind;       /* rl_env_kind */
-    int32_t map8x8;     /* FrozenLake: 0 = MAP_4X4, 1 = MAP_8X8 (frozen_lake.rs:23-28) */
+    int32_t map8x8;     /* FrozenLake: 0 = MAP_4X4, 1 = MAP_8X8 (frozen_lake.rs:23-28), or an id
+                           from rl_map_register (>= 2): the caller's own map */
     int32_t slippery;   /* FrozenLake --stochastic_env */
     uint32_t max_steps; /* truncation (frozen_lake.rs:119); ignored by Blackjack */
 } rl_env_config;
@@ -220,6 +221,30 @@ uint64_t rl_obs_to_reference(int32_t env_kind, uint32_t dense_state);
 /* the inverse: a reference observation (usize; Blackjack: its fxhash id) as the
  * dense state index; RL_E_ARG when it is none of the env's observations */
 int rl_obs_from_reference(int32_t env_kind, uint64_t obs, uint32_t *dense_state);
+/* -------- caller-supplied FrozenLake maps (additive to ABI 7)
+ * FrozenLakeEnv::new / FrozenLakeEditedEnv::new take any map (frozen_lake.rs:48-102,
+ * frozen_lake_edited.rs:168-224): any number of rows and columns (state = row *
+ * ncol + col) and any number of 'S' cells, of which Env::reset draws one
+ * (frozen_lake.rs:106-113, frozen_lake_edited.rs:228-236).  A map is registered
+ * once per process and named by its id in rl_env_config.map8x8; every entry point
+ * that takes an rl_env_config then works on it.  The registry is guarded by a mutex
+ * (any thread may register), keeps its maps for the life of the process and never
+ * reuses an id.
+ * Draws: reset draws one uniform01 only when the map has two or more 'S' cells; one
+ * 'S' anywhere is a fixed start and no 'S' starts every episode at cell 0 (the
+ * reference's all-false argmax, utils.rs:33-43), neither drawn.
+ * Limit: at most RL_MAP_MAX_CELLS cells — the packed transition table holds a
+ * 6-bit next state and the traces pair pool tags (state, action) pairs with 8 bits
+ * (S * A <= 256).  Larger maps would need a second table format and are rejected.
+ * RL_E_ARG (with a message) for: zero rows or columns, ragged rows, a letter outside
+ * SFHG, more than RL_MAP_MAX_CELLS cells, an unknown id; all before any HIP call. */
+#define RL_MAP_MAX_CELLS 64
+/* FrozenLakeEnv::new / FrozenLakeEditedEnv::new with the caller's map: rows of equal
+ * length over {S,F,H,G}.  *map_id >= 2; the same rows give the same id again. */
+int rl_map_register(const char *const *rows, uint32_t n_rows, int32_t *map_id);
+/* rows x cols and the cells (row-major, no terminators) of a map id; 0 / 1 are the
+ * built-ins.  cells may be NULL (dimensions only); else n must be rows * cols. */
+int rl_map_info(int32_t map_id, uint32_t *n_rows, uint32_t *n_cols, char *cells, size_t n);
 /* |S| and COUNT (Env::action_size, src/env.rs:20-22) for an env config */
 int rl_env_dims(const rl_env_config *cfg, uint32_t *n_states, uint32_t *n_actions);
 /* Host-side export of the packed device transition tables, decoded to the

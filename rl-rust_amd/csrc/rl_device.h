@@ -656,6 +656,25 @@ __device__ __forceinline__ uint32_t start_state(const EnvTables &t, double u) {
     return t.fixed_start >= 0 ? (uint32_t)t.fixed_start : cdf_search(t.cdf, t.n_start, u);
 }
 
+// Registered FrozenLake maps with two or more 'S' cells: categorical_sample over
+// the initial-state distribution (utils.rs:33-43) as a search of the start list,
+// t.cdf = [n_start running sums][n_start u32 cells] (rl_kparams.h).  The running
+// sum changes at the 'S' cells only, so the first cell whose sum exceeds u is the
+// full scan's first index; when none does (the last sum can round below the
+// largest u) the all-false argmax gives index 0.  n_start is uniform, the loop
+// body a select: every lane of a wave reads the same (broadcast) words.
+__device__ __forceinline__ uint32_t start_list_search(const EnvTables &t, double u) {
+    const uint32_t *cells = (const uint32_t *)(t.cdf + t.n_start);
+    uint32_t c = 0;
+    bool found = false;
+    for (uint32_t j = 0; j < t.n_start; ++j) {
+        const bool hit = !found && t.cdf[j] > u;
+        c = hit ? cells[j] : c;
+        found = found || hit;
+    }
+    return c;
+}
+
 template <int ENV> struct EnvDev;
 
 // FrozenLakeEnv (src/env/frozen_lake.rs).  trans[s*4+a]: 3 outcome bytes
@@ -670,13 +689,32 @@ template <int ENV> struct EnvDev;
 // FrozenLakeEdited (:227-231).
 // The outcome byte's reward bit means 1.0 (FrozenLake) or 10.0 (edited; else -1.0).
 // w: the table word trans[(pos, a)], read by the caller (possibly a step ahead)
-template <bool EDITED, int SLIP, bool AM>
+// MAPS (a registered map, ENV_FL_MAP / ENV_FLE_MAP): a RESET lane lands on the
+// map's start — fixed_start, or where the map has two or more 'S' cells the
+// categorical draw of frozen_lake.rs:107-109 over the start list.  A lane resets
+// or steps, never both, so the reset's draw and the step's share ONE draw site:
+// the lanes that need a value draw it under one test and both uses are selects
+// (no reset / step branch per lane).
+template <bool EDITED, int SLIP, bool AM, bool MAPS = false>
 __device__ __forceinline__ void fl_advance(bool doR, bool doS, uint32_t &pos, uint32_t &z, uint32_t w, Rng &r,
                                            const EnvTables &t, uint32_t &s2, double &rew, bool &term) {
     const bool trunc = doS && z >= t.max_steps;
     const bool st = doS && !trunc;
-    uint32_t i = 0;
-    if (SLIP == 1 || (SLIP < 0 && t.slippery)) {      // the only draw whose value is used
+    uint32_t i = 0, s0 = 0;
+    if constexpr (MAPS) {
+        const bool slip = SLIP == 1 || (SLIP < 0 && t.slippery);
+        const bool drawn = t.fixed_start < 0;          // uniform over the launch
+        s0 = drawn ? 0u : (uint32_t)t.fixed_start;
+        if ((slip && st) || (drawn && doR)) {
+            const double u = uniform01(r);
+            const uint32_t iu = (t.th1 > u) ? 0u : (t.th2 > u) ? 1u : (t.th3 > u) ? 2u : 0u;
+            i = (st && (w & (1u << 24))) ? iu : 0u;
+            if (drawn) {
+                const uint32_t c = start_list_search(t, u);
+                s0 = doR ? c : 0u;
+            }
+        }
+    } else if (SLIP == 1 || (SLIP < 0 && t.slippery)) {      // the only draw whose value is used
         if (st) {
             const double u = uniform01(r);
             if (w & (1u << 24)) i = (t.th1 > u) ? 0u : (t.th2 > u) ? 1u : (t.th3 > u) ? 2u : 0u;
@@ -684,7 +722,7 @@ __device__ __forceinline__ void fl_advance(bool doR, bool doS, uint32_t &pos, ui
     }
     const uint32_t o = (w >> (8 * i)) & 0xffu;
     const double r_bit = EDITED ? 10.0 : 1.0, r_else = EDITED ? -1.0 : 0.0;
-    s2 = st ? (o & 63u) : ((EDITED && trunc) ? pos : 0u);
+    s2 = st ? (o & 63u) : ((EDITED && trunc) ? pos : (MAPS && doR ? s0 : 0u));
     rew = st ? ((o & 64u) ? r_bit : r_else) : ((EDITED && trunc) ? -1.0 : 0.0);
     term = trunc || (st && (o & 128u) != 0u);
     z = doR ? 0u : (st ? z + 1u : z);
@@ -750,6 +788,29 @@ template <> struct EnvDev<RL_ENV_FROZEN_LAKE_EDITED> {
         pos = s2;
     }
 };
+
+// FrozenLakeEnv / FrozenLakeEditedEnv on a registered map (rl_map_register): the
+// built-in envs' tables and step, and the reset the reference's constructor gives
+// any map (frozen_lake.rs:52-65,106-113; frozen_lake_edited.rs:228-236): one 'S'
+// anywhere is a fixed start and no 'S' the all-false argmax's cell 0, neither
+// drawn; two or more 'S' cells draw one uniform01 (DESIGN §2 "draws").  The
+// slippery flag is read at run time (SLIP = -1) to bound the instantiations.
+template <int BASE> struct EnvDevMap {
+    static constexpr int A = 4;
+    __device__ static __forceinline__ uint32_t reset(uint32_t &z, Rng &r, const EnvTables &t) {
+        z = 0;
+        if (t.fixed_start >= 0) return (uint32_t)t.fixed_start;
+        return start_list_search(t, uniform01(r));
+    }
+    template <int SLIP = -1, bool AM = false>
+    __device__ static __forceinline__ void step(uint32_t &pos, uint32_t &z, uint32_t a, Rng &r,
+                                                const EnvTables &t, uint32_t &s2, double &rew,
+                                                bool &term) {
+        EnvDev<BASE>::template step<SLIP, AM>(pos, z, a, r, t, s2, rew, term);
+    }
+};
+template <> struct EnvDev<ENV_FL_MAP> : EnvDevMap<RL_ENV_FROZEN_LAKE> {};
+template <> struct EnvDev<ENV_FLE_MAP> : EnvDevMap<RL_ENV_FROZEN_LAKE_EDITED> {};
 
 // CliffWalkingEnv (src/env/cliff_walking.rs): deterministic, no RNG.
 // trans[s*4+a]: bits 0-5 next, bit 6 reward -100 (else -1), bit 7 terminated.

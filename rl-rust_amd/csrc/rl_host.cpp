@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -49,8 +50,16 @@ struct EnvHost {
     double th1 = 0, th2 = 0, th3 = 0, trunc_reward = 0;
     int32_t fixed_start = -1;     // categorical_sample over `cdf` is constant (single start state)
     int32_t slippery = 0;         // FrozenLake with stochastic rows
-    const char *const *map = nullptr;   // FrozenLake / FrozenLakeEdited grid (n x n)
-    int n = 0;
+    std::vector<std::string> map;   // FrozenLake / FrozenLakeEdited grid (nrow x ncol); empty otherwise
+    int nrow = 0, ncol = 0;
+    int kenv = 0;                 // kernel-side env id (rl_kparams.h): kind, or ENV_FL_MAP / ENV_FLE_MAP
+    // registered maps with two or more 'S' cells: the start list the device searches,
+    // [n_list f64 running sums][n_list u32 cells] packed in f64 words (rl_kparams.h)
+    std::vector<double> start_list;
+    uint32_t n_list = 0;
+    // what the device reads as KParams::start_cdf / n_start
+    const std::vector<double> &dev_cdf() const { return env_map_start(kenv) ? start_list : cdf; }
+    uint32_t dev_n_start() const { return env_map_start(kenv) ? n_list : (uint32_t)cdf.size(); }
 };
 
 const char *const kFL4[] = {"SFFF", "FHFH", "FFFH", "HFFG"};                     // frozen_lake.rs:23
@@ -76,15 +85,16 @@ void grid_move(int nrow, int ncol, int row, int col, int a, int &nr, int &nc) {
 // FrozenLakeTerrain of a cell / of the neighbour in direction a, WALL off the
 // grid (src/env/frozen_lake_edited.rs get_obs :115-144, get_terrain :146-162)
 enum { kStart = 0, kWall = 1, kHole = 2, kGround = 3, kGoal = 4 };
-int terrain(const char *const *map, int row, int col) {
+using Grid = std::vector<std::string>;
+int terrain(const Grid &map, int row, int col) {
     const char ch = map[row][col];
     return ch == 'S' ? kStart : ch == 'G' ? kGoal : ch == 'H' ? kHole : kGround;
 }
-int neighbour(const char *const *map, int n, int row, int col, int a) {
+int neighbour(const Grid &map, int nrow, int ncol, int row, int col, int a) {
     switch (a) {
     case 0: return col == 0 ? kWall : terrain(map, row, col - 1);
-    case 1: return row == n - 1 ? kWall : terrain(map, row + 1, col);
-    case 2: return col == n - 1 ? kWall : terrain(map, row, col + 1);
+    case 1: return row == nrow - 1 ? kWall : terrain(map, row + 1, col);
+    case 2: return col == ncol - 1 ? kWall : terrain(map, row, col + 1);
     default: return row == 0 ? kWall : terrain(map, row - 1, col);
     }
 }
@@ -135,39 +145,63 @@ bool taxi_start_checked(const EnvHost &e) {
     return ok == 1;
 }
 
+// The process-wide map registry (rl.h rl_map_register): ids 0 / 1 are MAP_4X4 /
+// MAP_8X8, registered maps get 2, 3, ... in registration order and keep them for
+// the life of the process (nothing is ever removed, so an id is never reused).
+std::mutex g_map_mu;
+std::vector<Grid> &map_registry() {
+    static std::vector<Grid> maps = {Grid(kFL4, kFL4 + 4), Grid(kFL8, kFL8 + 8)};
+    return maps;
+}
+bool map_lookup(int32_t id, Grid &out) {
+    std::lock_guard<std::mutex> lock(g_map_mu);
+    const std::vector<Grid> &maps = map_registry();
+    if (id < 0 || (size_t)id >= maps.size()) return false;
+    out = maps[(size_t)id];
+    return true;
+}
+
 int build_env(const rl_env_config &c, EnvHost &e) {
     e = EnvHost();
     e.kind = c.kind;
+    e.kenv = c.kind;
     e.max_steps = c.max_steps;
     if (c.kind == RL_ENV_FROZEN_LAKE || c.kind == RL_ENV_FROZEN_LAKE_EDITED) {
-        const char *const *map = c.map8x8 ? kFL8 : kFL4;
-        const int n = c.map8x8 ? 8 : 4;
         const bool edited = c.kind == RL_ENV_FROZEN_LAKE_EDITED;
-        e.map = map;
-        e.n = n;
-        e.S = n * n;
+        if (!map_lookup(c.map8x8, e.map))
+            return fail(RL_E_ARG, "unknown FrozenLake map id " + std::to_string(c.map8x8) +
+                                      " (0 = MAP_4X4, 1 = MAP_8X8, else an id from rl_map_register)");
+        const Grid &map = e.map;
+        // nrow x ncol, state = row * ncol + col (frozen_lake.rs:49-50, utils.rs:45-51)
+        const int nrow = (int)map.size(), ncol = (int)map[0].size();
+        e.nrow = nrow;
+        e.ncol = ncol;
+        // a registered map runs the kernels with the start variant (rl_kparams.h), a
+        // built-in one exactly the instantiations it always ran
+        if (c.map8x8 >= 2) e.kenv = edited ? ENV_FLE_MAP : ENV_FL_MAP;
+        e.S = (uint32_t)(nrow * ncol);
         e.A = 4;
         e.trans.assign(e.S * 4, 0);
         int n_start = 0;
-        for (int i = 0; i < n * n; ++i) n_start += map[i / n][i % n] == 'S';
-        e.start.assign(e.S, 0.0);
-        for (int i = 0; i < n * n; ++i)
-            if (map[i / n][i % n] == 'S') e.start[i] = 1.0 / n_start;
+        for (int i = 0; i < nrow * ncol; ++i) n_start += map[i / ncol][i % ncol] == 'S';
+        e.start.assign(e.S, 0.0);   // frozen_lake.rs:52-65: 1/k on each of the k 'S' cells
+        for (int i = 0; i < nrow * ncol; ++i)
+            if (map[i / ncol][i % ncol] == 'S') e.start[i] = 1.0 / n_start;
         auto outcome = [&](int row, int col, int a) -> uint32_t {
             int nr, nc;
-            grid_move(n, n, row, col, a, nr, nc);
+            grid_move(nrow, ncol, row, col, a, nr, nc);
             if (edited) {   // update_probability_matrix (frozen_lake_edited.rs:94-113): judged by
                             // the terrain in the moved direction; 10.0 onto G, else -1.0
-                const int t = neighbour(map, n, row, col, a);
-                return (uint32_t)(nr * n + nc) | (t == kGoal ? 64u : 0u) | ((t == kGoal || t == kHole) ? 128u : 0u);
+                const int t = neighbour(map, nrow, ncol, row, col, a);
+                return (uint32_t)(nr * ncol + nc) | (t == kGoal ? 64u : 0u) | ((t == kGoal || t == kHole) ? 128u : 0u);
             }
             const char ch = map[nr][nc];
-            return (uint32_t)(nr * n + nc) | (ch == 'G' ? 64u : 0u) | ((ch == 'G' || ch == 'H') ? 128u : 0u);
+            return (uint32_t)(nr * ncol + nc) | (ch == 'G' ? 64u : 0u) | ((ch == 'G' || ch == 'H') ? 128u : 0u);
         };
-        for (int row = 0; row < n; ++row)
-            for (int col = 0; col < n; ++col)
+        for (int row = 0; row < nrow; ++row)
+            for (int col = 0; col < ncol; ++col)
                 for (int a = 0; a < 4; ++a) {
-                    const int s = row * n + col;
+                    const int s = row * ncol + col;
                     const char ch = map[row][col];
                     uint32_t w;
                     if (ch == 'G' || ch == 'H') w = (uint32_t)s | 128u;              // (1.0, s, 0, true)
@@ -246,20 +280,51 @@ int build_env(const rl_env_config &c, EnvHost &e) {
     }
     if (!e.start.empty()) finish_cdf(e);
     if (c.kind == RL_ENV_TAXI && !taxi_start_checked(e)) return fail(RL_E_STATE, "taxi_start differs from categorical_sample");
-    // the device FrozenLake resets assume the built-in maps' single start at 0 (rl_device.h)
-    if (e.map && e.fixed_start != 0) return fail(RL_E_ARG, "FrozenLake map must start at position 0");
+    if (env_map_start(e.kenv)) {
+        // Env::reset on a registered map (DESIGN §2 "draws"): no 'S' is the all-false
+        // argmax's cell 0 (utils.rs:33-43), one 'S' a fixed start, neither drawn; two
+        // or more draw one uniform01 and search the list of the 'S' cells with their
+        // running sums — the sum changes nowhere else, so this is the full scan.
+        std::vector<uint32_t> cells;
+        for (uint32_t i = 0; i < e.S; ++i)
+            if (e.start[i] != 0.0) cells.push_back(i);
+        if (cells.empty()) e.fixed_start = 0;
+        else if (cells.size() == 1) e.fixed_start = (int32_t)cells[0];
+        else {
+            e.fixed_start = -1;
+            e.n_list = (uint32_t)cells.size();
+            e.start_list.assign(e.n_list + (e.n_list + 1) / 2, 0.0);
+            for (uint32_t j = 0; j < e.n_list; ++j) e.start_list[j] = e.cdf[cells[j]];
+            std::memcpy(e.start_list.data() + e.n_list, cells.data(), cells.size() * sizeof(uint32_t));
+            // the list against the full scan at every boundary and its neighbours
+            std::vector<double> us = {0.0, std::nextafter(1.0, 0.0)};
+            for (uint32_t j = 0; j < e.n_list; ++j)
+                for (double x : {e.start_list[j], std::nextafter(e.start_list[j], 0.0), std::nextafter(e.start_list[j], 2.0)})
+                    if (x >= 0.0 && x < 1.0) us.push_back(x);
+            for (double u : us) {
+                uint32_t got = 0;
+                for (uint32_t j = 0; j < e.n_list; ++j)
+                    if (e.start_list[j] > u) { got = cells[j]; break; }
+                if (got != linear_sample(e.cdf, u)) return fail(RL_E_STATE, "start list differs from categorical_sample");
+            }
+        }
+    } else if (!e.map.empty() && e.fixed_start != 0) {
+        // the built-in maps' kernels reset to the constant 0 (rl_device.h)
+        return fail(RL_E_STATE, "built-in FrozenLake map does not start at position 0");
+    }
     return RL_OK;
 }
 
 // NeuralPolicy input features of every dense state (rl.h rl_input_adapter)
 int net_feature_table(const rl_env_config &c, const EnvHost &e, int input, std::vector<double> &feat, uint32_t &n_in) {
     if (input == RL_INPUT_FL_OBS) {
-        if (!e.map) return fail(RL_E_ARG, "the FrozenLakeObs adapter needs FrozenLake / FrozenLakeEdited");
+        if (e.map.empty()) return fail(RL_E_ARG, "the FrozenLakeObs adapter needs FrozenLake / FrozenLakeEdited");
         n_in = 6;
         feat.assign((size_t)e.S * 6, 0.0);
         for (uint32_t s = 0; s < e.S; ++s) {
-            const int row = (int)s / e.n, col = (int)s % e.n;
-            for (int a = 0; a < 4; ++a) feat[s * 6 + a] = terrain_value(neighbour(e.map, e.n, row, col, a));
+            const int row = (int)s / e.ncol, col = (int)s % e.ncol;   // x = row, y = col (frozen_lake_edited.rs:146-147)
+            for (int a = 0; a < 4; ++a)
+                feat[s * 6 + a] = terrain_value(neighbour(e.map, e.nrow, e.ncol, row, col, a));
             feat[s * 6 + 4] = (double)row;
             feat[s * 6 + 5] = (double)col;
         }
@@ -505,7 +570,7 @@ int peer_check(rl_agent *a);
 int peer_selftest(rl_agent *a, bool *ok);
 
 int agent_select_kernel(rl_agent *a) {
-    a->fn = lookup_train(a->cfg.env.kind, a->cfg.agent, a->cfg.policy, a->cfg.selector, a->cfg.algo,
+    a->fn = lookup_train(a->eh.kenv, a->cfg.agent, a->cfg.policy, a->cfg.selector, a->cfg.algo,
                          a->priv ? 1 : 0);
     if (!a->fn) return fail(RL_E_ARG, "no kernel for this (env, agent, policy, selector)");
     if (!a->priv && a->cfg.selector == RL_SEL_UCB && a->cfg.algo == RL_ALGO_EXPECTED_SARSA &&
@@ -514,8 +579,8 @@ int agent_select_kernel(rl_agent *a) {
     if (a->priv) {
         a->block = dim3(256);
         a->grid = dim3((a->L + 255) / 256);
-        a->smem = private_smem_bytes(a->cfg.env.kind, a->cfg.agent, a->cfg.policy, a->cfg.selector, a->S,
-                                     a->A, (uint32_t)a->eh.cdf.size());
+        a->smem = private_smem_bytes(a->eh.kenv, a->cfg.agent, a->cfg.policy, a->cfg.selector, a->S,
+                                     a->A, a->eh.dev_n_start());
         // small tables (FrozenLake, CliffWalking; single or double): the launch's
         // lanes keep their Q in LDS (k_train_private_lds), 4 waves of priv_lpw lanes
         // per block (8: 32 lanes, 50 KB for CliffWalking, 3 blocks per CU); slots of
@@ -599,8 +664,8 @@ int agent_select_kernel(rl_agent *a) {
             int ncu = 256;
             (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, a->device);
             const uint64_t groups = a->grid.x, per_cu = (groups + (uint64_t)ncu - 1) / (uint64_t)ncu;
-            const size_t base = shared_smem_bytes(a->cfg.env.kind, a->cfg.agent, a->cfg.policy, a->cfg.selector,
-                                                  a->cfg.algo, a->S, a->A, (uint32_t)a->eh.cdf.size(), a->block.x, 0,
+            const size_t base = shared_smem_bytes(a->eh.kenv, a->cfg.agent, a->cfg.policy, a->cfg.selector,
+                                                  a->cfg.algo, a->S, a->A, a->eh.dev_n_start(), a->block.x, 0,
                                                   a->qrepr == RL_QREPR_F64, a->kp.ucb_pack);
             // the groups that can be resident at all: the kernel's register-limited
             // occupancy (without the pair slots), not only the 32-wave cap — cfg 4 at
@@ -631,8 +696,8 @@ int agent_select_kernel(rl_agent *a) {
                 const int v = atoi(e);
                 if (v >= 0 && v <= 150) a->trc_kb_v[epi] = (uint32_t)v;
             }
-            a->smem_v[epi] = shared_smem_bytes(a->cfg.env.kind, a->cfg.agent, a->cfg.policy, a->cfg.selector,
-                                               a->cfg.algo, a->S, a->A, (uint32_t)a->eh.cdf.size(), a->block.x,
+            a->smem_v[epi] = shared_smem_bytes(a->eh.kenv, a->cfg.agent, a->cfg.policy, a->cfg.selector,
+                                               a->cfg.algo, a->S, a->A, a->eh.dev_n_start(), a->block.x,
                                                a->trc_kb_v[epi], a->qrepr == RL_QREPR_F64, a->kp.ucb_pack);
             if (a->smem_v[epi] > 160 * 1024) return fail(RL_E_ARG, "learner-group tables exceed the 160 KiB LDS");
         }
@@ -931,10 +996,10 @@ int launch_train_kernel(rl_agent *a, bool *merge = nullptr) {
     // while a lane's list survives the launch boundary (p.tcnt).  The HBM slots'
     // index (slot_of) and visited-state bitmap (vbits) are kept only for slots >=
     // cap, so a launch with another cap rebuilds them for its own first
-    if (!a->priv && a->vbits && a->tcnt && pair_slot_index_env(a->cfg.env.kind) &&
+    if (!a->priv && a->vbits && a->tcnt && pair_slot_index_env(a->eh.kenv) &&
         layout_sparse_traces(a->cfg.agent, a->cfg.selector, a->cfg.algo, 0)) {
-        const uint32_t cap = shared_pair_cap(a->cfg.env.kind, a->cfg.agent, a->cfg.policy, a->cfg.selector,
-                                             a->cfg.algo, a->S, a->A, (uint32_t)a->eh.cdf.size(), a->block.x,
+        const uint32_t cap = shared_pair_cap(a->eh.kenv, a->cfg.agent, a->cfg.policy, a->cfg.selector,
+                                             a->cfg.algo, a->S, a->A, a->eh.dev_n_start(), a->block.x,
                                              a->kp.trc_kb, a->qrepr == RL_QREPR_F64, a->kp.ucb_pack);
         if (a->pair_cap_last != UINT32_MAX && cap != a->pair_cap_last) {
             launch_pair_reindex(a->kp, cap, a->stream);
@@ -1227,6 +1292,54 @@ int rl_obs_from_reference(int32_t env_kind, uint64_t obs, uint32_t *dense_state)
     return RL_OK;
 }
 
+int rl_map_register(const char *const *rows, uint32_t n_rows, int32_t *map_id) {
+    if (!rows || !map_id) return fail(RL_E_ARG, "null argument");
+    if (n_rows == 0) return fail(RL_E_ARG, "a map needs at least one row");
+    Grid g;
+    for (uint32_t r = 0; r < n_rows; ++r) {
+        if (!rows[r]) return fail(RL_E_ARG, "null map row " + std::to_string(r));
+        // the length is bounded while it is measured: a row is never read past the cell limit
+        const size_t len = strnlen(rows[r], (size_t)RL_MAP_MAX_CELLS + 1);
+        if (len == 0) return fail(RL_E_ARG, "map row " + std::to_string(r) + " has zero columns");
+        if (r > 0 && len != g[0].size())
+            return fail(RL_E_ARG, "ragged map: row " + std::to_string(r) + " has " +
+                                      (len > RL_MAP_MAX_CELLS ? "more than " + std::to_string(RL_MAP_MAX_CELLS)
+                                                              : std::to_string(len)) +
+                                      " columns, row 0 has " + std::to_string(g[0].size()));
+        if ((size_t)n_rows * len > RL_MAP_MAX_CELLS)
+            return fail(RL_E_ARG, "map has more than RL_MAP_MAX_CELLS (" + std::to_string(RL_MAP_MAX_CELLS) + ") cells");
+        for (size_t i = 0; i < len; ++i) {
+            const char ch = rows[r][i];
+            if (ch != 'S' && ch != 'F' && ch != 'H' && ch != 'G')
+                return fail(RL_E_ARG, std::string("map letter outside SFHG at row ") + std::to_string(r) + ", column " +
+                                          std::to_string(i));
+        }
+        g.emplace_back(rows[r], len);
+    }
+    std::lock_guard<std::mutex> lock(g_map_mu);
+    std::vector<Grid> &maps = map_registry();
+    for (size_t i = 2; i < maps.size(); ++i)
+        if (maps[i] == g) { *map_id = (int32_t)i; return RL_OK; }
+    if (maps.size() >= (size_t)INT32_MAX) return fail(RL_E_ARG, "map registry full");
+    maps.push_back(std::move(g));
+    *map_id = (int32_t)(maps.size() - 1);
+    return RL_OK;
+}
+
+int rl_map_info(int32_t map_id, uint32_t *n_rows, uint32_t *n_cols, char *cells, size_t n) {
+    Grid g;
+    if (!map_lookup(map_id, g))
+        return fail(RL_E_ARG, "unknown FrozenLake map id " + std::to_string(map_id));
+    const size_t nr = g.size(), nc = g[0].size();
+    if (n_rows) *n_rows = (uint32_t)nr;
+    if (n_cols) *n_cols = (uint32_t)nc;
+    if (cells) {
+        if (n != nr * nc) return fail(RL_E_ARG, "cells must hold rows * cols = " + std::to_string(nr * nc) + " chars");
+        for (size_t r = 0; r < nr; ++r) std::memcpy(cells + r * nc, g[r].data(), nc);
+    }
+    return RL_OK;
+}
+
 int rl_env_dims(const rl_env_config *cfg, uint32_t *S, uint32_t *A) {
     if (!cfg || !S || !A) return fail(RL_E_ARG, "null argument");
     EnvHost e;
@@ -1254,7 +1367,7 @@ int rl_env_table(const rl_env_config *cfg, double *prob, uint32_t *next, double 
             uint8_t tm[3] = {0, 0, 0};
             if (e.kind == RL_ENV_FROZEN_LAKE || e.kind == RL_ENV_FROZEN_LAKE_EDITED) {
                 const bool edited = e.kind == RL_ENV_FROZEN_LAKE_EDITED;
-                const char cell = e.map[s / e.n][s % e.n];
+                const char cell = e.map[s / e.ncol][s % e.ncol];
                 const int n = (w >> 24) & 1 ? 3 : 1;
                 for (int i = 0; i < n; ++i) {
                     const uint32_t o = (w >> (8 * i)) & 0xffu;
@@ -1302,18 +1415,18 @@ int rl_env_create(const rl_env_config *cfg, uint32_t n, uint64_t seed, uint64_t 
         return bad(fail(RL_E_HIP, "hipStreamCreate failed"));
     if ((rc = dalloc(&e->core, n)) || (rc = dalloc(&e->rng, n)) || (rc = dalloc(&e->act_d, n)) ||
         (rc = dalloc(&e->obs_d, n)) || (rc = dalloc(&e->rew_d, n)) || (rc = dalloc(&e->term_d, n)) ||
-        (rc = dalloc(&e->trans, e->eh.trans.size())) || (rc = dalloc(&e->cdf, e->eh.cdf.size())))
+        (rc = dalloc(&e->trans, e->eh.trans.size())) || (rc = dalloc(&e->cdf, e->eh.dev_cdf().size())))
         return bad(rc);
     if (!e->eh.trans.empty() &&
         hipMemcpy(e->trans, e->eh.trans.data(), e->eh.trans.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
         return bad(fail(RL_E_HIP, "table upload"));
-    if (!e->eh.cdf.empty() &&
-        hipMemcpy(e->cdf, e->eh.cdf.data(), e->eh.cdf.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
+    if (!e->eh.dev_cdf().empty() &&
+        hipMemcpy(e->cdf, e->eh.dev_cdf().data(), e->eh.dev_cdf().size() * 8, hipMemcpyHostToDevice) != hipSuccess)
         return bad(fail(RL_E_HIP, "table upload"));
     KParams &p = e->kp;
     p.L = n; p.S = e->eh.S; p.A = e->eh.A; p.P = 1;
     p.core = e->core; p.rng = e->rng;
-    p.trans = e->trans; p.start_cdf = e->cdf; p.n_start = (uint32_t)e->eh.cdf.size();
+    p.trans = e->trans; p.start_cdf = e->cdf; p.n_start = e->eh.dev_n_start();
     p.fixed_start = e->eh.fixed_start;
     p.slippery = e->eh.slippery;
     p.max_steps = e->eh.max_steps; p.th1 = e->eh.th1; p.th2 = e->eh.th2; p.th3 = e->eh.th3;
@@ -1375,7 +1488,7 @@ int rl_env_reset(rl_env *e, uint64_t *obs) {
     if (!e || !obs) return fail(RL_E_ARG, "null argument");
     hipStream_t st;
     if (int rc = env_stream(e, &st)) return rc;
-    launch_env_reset(e->cfg.kind, e->kp, st, e->obs_d);
+    launch_env_reset(e->eh.kenv, e->kp, st, e->obs_d);
     HIPC(hipGetLastError());
     HIPC(hipMemcpyAsync(obs, e->obs_d, e->L * 8, hipMemcpyDeviceToHost, st));
     HIPC(hipStreamSynchronize(st));
@@ -1395,7 +1508,7 @@ int rl_env_step(rl_env *e, const uint32_t *act, uint64_t *obs, double *rew, uint
         if (act[i] >= e->eh.A) return fail(RL_E_ARG, "action out of range");
     }
     HIPC(hipMemcpyAsync(e->act_d, act, e->L * 4, hipMemcpyHostToDevice, st));
-    launch_env_step(e->cfg.kind, e->kp, st, e->act_d, e->obs_d, e->rew_d, e->term_d, nullptr);
+    launch_env_step(e->eh.kenv, e->kp, st, e->act_d, e->obs_d, e->rew_d, e->term_d, nullptr);
     HIPC(hipGetLastError());
     HIPC(hipMemcpyAsync(obs, e->obs_d, e->L * 8, hipMemcpyDeviceToHost, st));
     HIPC(hipMemcpyAsync(rew, e->rew_d, e->L * 8, hipMemcpyDeviceToHost, st));
@@ -1418,7 +1531,7 @@ int rl_env_reset_lane(rl_env *e, uint32_t lane, uint64_t *obs) {
     if (int rc = view_ready_refresh(e, st)) return rc;   // the other lanes' readiness
     KParams p = e->kp;
     p.L = 1; p.core += lane; p.rng += lane;
-    launch_env_reset(e->cfg.kind, p, st, e->obs_d);
+    launch_env_reset(e->eh.kenv, p, st, e->obs_d);
     HIPC(hipGetLastError());
     HIPC(hipMemcpyAsync(obs, e->obs_d, 8, hipMemcpyDeviceToHost, st));
     HIPC(hipStreamSynchronize(st));
@@ -1438,7 +1551,7 @@ int rl_env_step_lane(rl_env *e, uint32_t lane, uint32_t action, uint64_t *obs, d
     KParams p = e->kp;
     p.L = 1; p.core += lane; p.rng += lane;
     HIPC(hipMemcpyAsync(e->act_d, &action, 4, hipMemcpyHostToDevice, st));
-    launch_env_step(e->cfg.kind, p, st, e->act_d, e->obs_d, e->rew_d, e->term_d, nullptr);
+    launch_env_step(e->eh.kenv, p, st, e->act_d, e->obs_d, e->rew_d, e->term_d, nullptr);
     HIPC(hipGetLastError());
     HIPC(hipMemcpyAsync(obs, e->obs_d, 8, hipMemcpyDeviceToHost, st));
     HIPC(hipMemcpyAsync(rew, e->rew_d, 8, hipMemcpyDeviceToHost, st));
@@ -1482,7 +1595,7 @@ int rl_agent_create(const rl_agent_config *cfg, rl_agent **out) {
     const size_t L = a->L, SA = (size_t)a->S * a->A, PSA = a->P * SA;
     if ((rc = dalloc(&a->core, L)) || (rc = dalloc(&a->rng, L)) || (rc = dalloc(&a->aux, L)) ||
         (rc = dalloc(&a->epi_reward, L)) || (rc = dalloc(&a->stats_d, STATS_W * STATS_REP)) ||
-        (rc = dalloc(&a->trans, a->eh.trans.size())) || (rc = dalloc(&a->cdf, a->eh.cdf.size())))
+        (rc = dalloc(&a->trans, a->eh.trans.size())) || (rc = dalloc(&a->cdf, a->eh.dev_cdf().size())))
         return bad(rc);
     a->neural = c.policy == RL_POLICY_NEURAL;
     if (a->neural) {
@@ -1537,8 +1650,8 @@ int rl_agent_create(const rl_agent_config *cfg, rl_agent **out) {
     if (!a->eh.trans.empty() &&
         hipMemcpy(a->trans, a->eh.trans.data(), a->eh.trans.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
         return bad(fail(RL_E_HIP, "table upload"));
-    if (!a->eh.cdf.empty() &&
-        hipMemcpy(a->cdf, a->eh.cdf.data(), a->eh.cdf.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
+    if (!a->eh.dev_cdf().empty() &&
+        hipMemcpy(a->cdf, a->eh.dev_cdf().data(), a->eh.dev_cdf().size() * 8, hipMemcpyHostToDevice) != hipSuccess)
         return bad(fail(RL_E_HIP, "table upload"));
     if (hipMemset(a->stats_d, 0, STATS_W * 8 * STATS_REP) != hipSuccess) return bad(fail(RL_E_HIP, "memset"));
     if ((rc = dalloc(&a->ctl_d, 3))) return bad(rc);
@@ -1560,7 +1673,7 @@ int rl_agent_create(const rl_agent_config *cfg, rl_agent **out) {
     p.net_w = a->net_w; p.feat = a->feat; p.n_in = a->n_in; p.n_hidden = c.net.hidden; p.n_params = a->n_params;
     p.act1 = c.net.act_hidden; p.act2 = c.net.act_out;
     p.trace = a->trace; p.tlist = a->tlist; p.slot_of = a->slot_of; p.tcnt = a->tcnt; p.vbits = a->vbits;
-    p.trans = a->trans; p.start_cdf = a->cdf; p.n_start = (uint32_t)a->eh.cdf.size();
+    p.trans = a->trans; p.start_cdf = a->cdf; p.n_start = a->eh.dev_n_start();
     p.fixed_start = a->eh.fixed_start;
     p.slippery = a->eh.slippery;
     p.max_steps = a->eh.max_steps; p.th1 = a->eh.th1; p.th2 = a->eh.th2; p.th3 = a->eh.th3;
@@ -2026,7 +2139,7 @@ int rl_agent_env(rl_agent *a, rl_env **out) {
     KParams &p = e->kp;
     p.L = e->L; p.S = a->S; p.A = a->A; p.P = 1;
     p.core = a->core; p.rng = a->rng;
-    p.trans = a->trans; p.start_cdf = a->cdf; p.n_start = (uint32_t)a->eh.cdf.size();
+    p.trans = a->trans; p.start_cdf = a->cdf; p.n_start = a->eh.dev_n_start();
     p.fixed_start = a->eh.fixed_start;
     p.slippery = a->eh.slippery;
     p.max_steps = a->eh.max_steps; p.th1 = a->eh.th1; p.th2 = a->eh.th2; p.th3 = a->eh.th3;

@@ -26,6 +26,20 @@ constexpr uint32_t STATS_REP = 64;
 constexpr uint32_t STATS_W = 16;
 constexpr uint32_t ACC_CLAMP = 8, ACC_SAT = 9;
 
+// Kernel-side env ids.  rl_env_kind names the reference's envs; FrozenLake and
+// FrozenLakeEdited on a registered map (rl_map_register) run instantiations of
+// their own, whose reset honours KParams::fixed_start or draws over the map's 'S'
+// cells (rl_device.h EnvDev<ENV_FL_MAP>).  The built-in maps keep the kernels of
+// RL_ENV_FROZEN_LAKE / RL_ENV_FROZEN_LAKE_EDITED, whose reset is the constant 0.
+constexpr int ENV_FL_MAP = 16, ENV_FLE_MAP = 17;
+__host__ __device__ constexpr bool env_fl_plain(int e) { return e == RL_ENV_FROZEN_LAKE || e == ENV_FL_MAP; }
+__host__ __device__ constexpr bool env_fl_edited(int e) { return e == RL_ENV_FROZEN_LAKE_EDITED || e == ENV_FLE_MAP; }
+__host__ __device__ constexpr bool env_fl_family(int e) { return env_fl_plain(e) || env_fl_edited(e); }
+__host__ __device__ constexpr bool env_map_start(int e) { return e == ENV_FL_MAP || e == ENV_FLE_MAP; }
+// the start list of a registered map with two or more 'S' cells, one buffer:
+// [n_start f64 running sums][n_start u32 cells] (HBM; the shared kernels copy it to LDS)
+__host__ __device__ constexpr uint32_t start_list_bytes(uint32_t n_start) { return n_start * 12u; }
+
 // lane core record (uint4, SoA over lanes):
 //   x = s (dense state), y = flags word below, z = env word (curr_step | blackjack hand),
 //   w = training episodes finished in the current train() call
@@ -111,7 +125,8 @@ struct KParams {
     int32_t act1, act2;    // rl_activation of the hidden / output layer
     // env tables
     const uint32_t *trans; // [S][A] packed
-    const double *start_cdf;   // [n_start] running sums (categorical_sample); HBM
+    const double *start_cdf;   // [n_start] running sums (categorical_sample); HBM.  Registered maps:
+                               // the start list (start_list_bytes above), n_start = its cells
     uint32_t n_start;
     int32_t fixed_start;   // >= 0 when the start distribution is a single state
     int32_t slippery;      // FrozenLake with stochastic rows (else the per-step draw is skipped over)

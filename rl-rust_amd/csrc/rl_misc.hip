@@ -10,6 +10,8 @@ train_launch_fn train_table_cliff_walking(int, int, int, int, int);
 train_launch_fn train_table_taxi(int, int, int, int, int);
 train_launch_fn train_table_blackjack(int, int, int, int, int);
 train_launch_fn train_table_frozen_lake_edited(int, int, int, int, int);
+train_launch_fn train_table_frozen_lake_map(int, int, int, int, int);
+train_launch_fn train_table_frozen_lake_edited_map(int, int, int, int, int);
 
 train_launch_fn lookup_train(int env, int agent, int policy, int sel, int algo, int priv) {
     switch (env) {
@@ -18,6 +20,8 @@ train_launch_fn lookup_train(int env, int agent, int policy, int sel, int algo, 
     case RL_ENV_TAXI: return train_table_taxi(agent, policy, sel, algo, priv);
     case RL_ENV_BLACKJACK: return train_table_blackjack(agent, policy, sel, algo, priv);
     case RL_ENV_FROZEN_LAKE_EDITED: return train_table_frozen_lake_edited(agent, policy, sel, algo, priv);
+    case ENV_FL_MAP: return train_table_frozen_lake_map(agent, policy, sel, algo, priv);
+    case ENV_FLE_MAP: return train_table_frozen_lake_edited_map(agent, policy, sel, algo, priv);
     }
     return nullptr;
 }
@@ -46,7 +50,7 @@ uint32_t shared_pair_cap(int env, int agent, int policy, int sel, int algo, uint
 // train_shared_body) and never read either
 bool pair_slot_index_env(int env) {
     return !(RLAMD_COOP_SWEEP && RLAMD_PAIR_BITS &&
-             (env == RL_ENV_CLIFF_WALKING || env == RL_ENV_FROZEN_LAKE || env == RL_ENV_FROZEN_LAKE_EDITED));
+             (env == RL_ENV_CLIFF_WALKING || env_fl_family(env)));
 }
 
 // ---------------------------------------------------------------- pair-trace re-index
@@ -556,6 +560,8 @@ void launch_env_reset(int env, const KParams &p, hipStream_t s, uint64_t *obs) {
     case RL_ENV_TAXI: hipLaunchKernelGGL(k_env_reset<RL_ENV_TAXI>, g, b, 0, s, p, obs); break;
     case RL_ENV_BLACKJACK: hipLaunchKernelGGL(k_env_reset<RL_ENV_BLACKJACK>, g, b, 0, s, p, obs); break;
     case RL_ENV_FROZEN_LAKE_EDITED: hipLaunchKernelGGL(k_env_reset<RL_ENV_FROZEN_LAKE_EDITED>, g, b, 0, s, p, obs); break;
+    case ENV_FL_MAP: hipLaunchKernelGGL(k_env_reset<ENV_FL_MAP>, g, b, 0, s, p, obs); break;
+    case ENV_FLE_MAP: hipLaunchKernelGGL(k_env_reset<ENV_FLE_MAP>, g, b, 0, s, p, obs); break;
     }
 }
 void launch_env_step(int env, const KParams &p, hipStream_t s, const uint32_t *act, uint64_t *obs,
@@ -567,6 +573,8 @@ void launch_env_step(int env, const KParams &p, hipStream_t s, const uint32_t *a
     case RL_ENV_TAXI: hipLaunchKernelGGL(k_env_step<RL_ENV_TAXI>, g, b, 0, s, p, act, obs, rew, term); break;
     case RL_ENV_BLACKJACK: hipLaunchKernelGGL(k_env_step<RL_ENV_BLACKJACK>, g, b, 0, s, p, act, obs, rew, term); break;
     case RL_ENV_FROZEN_LAKE_EDITED: hipLaunchKernelGGL(k_env_step<RL_ENV_FROZEN_LAKE_EDITED>, g, b, 0, s, p, act, obs, rew, term); break;
+    case ENV_FL_MAP: hipLaunchKernelGGL(k_env_step<ENV_FL_MAP>, g, b, 0, s, p, act, obs, rew, term); break;
+    case ENV_FLE_MAP: hipLaunchKernelGGL(k_env_step<ENV_FLE_MAP>, g, b, 0, s, p, act, obs, rew, term); break;
     }
 }
 

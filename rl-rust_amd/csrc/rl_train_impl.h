@@ -75,7 +75,7 @@ __host__ __device__ inline uint32_t bj_dense(uint32_t row) {      // LDS row -> 
 // Pair traces on small tables (FrozenLake, CliffWalking: S*A <= 256, so a pair id
 // is 8 bits) keep every wave's visited pairs in one pool (pair_pool below)
 __host__ __device__ constexpr bool pair_pool_env(int env) {
-    return env == RL_ENV_CLIFF_WALKING || env == RL_ENV_FROZEN_LAKE || env == RL_ENV_FROZEN_LAKE_EDITED;
+    return env == RL_ENV_CLIFF_WALKING || env_fl_family(env);
 }
 // Fixed-point single-table Q-learning (rl_device.h argmax_max, the fused argmax +
 // max of the target row) keeps an f64 image of every entry beside its int64 word:
@@ -192,10 +192,13 @@ __host__ __device__ inline SmemLayout smem_layout(int env, int P, int ucb, int t
     l.list = off; off += (shared_q && traces) ? align16(PSA * 2u) + 16u : 0u;
     l.rcp = off; off += align16(l.nrcp * 8u);
     l.tr = off; off += (env == RL_ENV_TAXI || env == RL_ENV_BLACKJACK) ? 0u : align16(SA * 4u);
-    // start distributions: FrozenLake's maps start at 0 (fixed_start), Taxi probes
-    // the HBM cdf (taxi_start), CliffWalking / Blackjack have none
-    (void)n_start;
+    // start distributions: FrozenLake's built-in maps start at 0 (fixed_start), Taxi
+    // probes the HBM cdf (taxi_start), CliffWalking / Blackjack have none; a registered
+    // FrozenLake map with two or more 'S' cells keeps its start list here in the
+    // shared kernels (rl_kparams.h start_list_bytes; the private kernels, which
+    // reset once per episode and lane, read the few words from HBM / L2)
     l.cdf = off;
+    off += (shared_q && env_map_start(env)) ? align16(start_list_bytes(n_start)) : 0u;
     // trc_kb KiB per group (KParams::trc_kb), at most S*A slots per lane
     // row strides padded by 2 / 1 entries (PairCache): one lane's consecutive
     // slots then sit in different LDS banks
@@ -751,6 +754,10 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
     }
     if constexpr (ENV != RL_ENV_TAXI && ENV != RL_ENV_BLACKJACK)
         for (uint32_t i = tid; i < SA; i += nthr) TR[lds_of(i)] = p.trans[i];
+    // registered map: the start list as u32 words (8-byte aligned: l.cdf is a multiple of 16)
+    if constexpr (env_map_start(ENV))
+        for (uint32_t i = tid; i < p.n_start * 3u; i += nthr)
+            ((uint32_t *)(smem + lay.cdf))[i] = ((const uint32_t *)p.start_cdf)[i];
     // row summaries (RLAMD_ROWMAX): in the sweep form only (the settle rewrites them)
     const bool sweep = SWEEP == 1 || PSAL <= nthr;   // SWEEP == 1: the host checked PSA <= block
     const bool rmx = QSH && RLAMD_ROWMAX && A == 4 && sweep;
@@ -767,6 +774,7 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
 
     EnvTables tabs;
     tabs.trans = TR; tabs.cdf = p.start_cdf; tabs.n_start = p.n_start; tabs.max_steps = p.max_steps;
+    if constexpr (env_map_start(ENV)) tabs.cdf = (const double *)(smem + lay.cdf);
     tabs.th1 = p.th1; tabs.th2 = p.th2; tabs.th3 = p.th3; tabs.trunc_reward = p.trunc_reward;
     tabs.fixed_start = p.fixed_start;
     tabs.slippery = p.slippery;
@@ -813,8 +821,7 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
     // sweep (the same f64 add, before its use), and "first pair of its state" is the
     // state's A bits
     constexpr bool PBITS = PAIRS && RLAMD_COOP_SWEEP && RLAMD_PAIR_BITS &&
-                           (ENV == RL_ENV_CLIFF_WALKING || ENV == RL_ENV_FROZEN_LAKE ||
-                            ENV == RL_ENV_FROZEN_LAKE_EDITED);
+                           (ENV == RL_ENV_CLIFF_WALKING || env_fl_family(ENV));
     constexpr int PBW = ENV == RL_ENV_CLIFF_WALKING ? 6 : 8;   // 48*4 / 64*4 pair ids
     // pair pool (small tables): the visited pairs of a wave's 64 lanes as ONE list of
     // items, tag = pair id (8 bits) | lane in wave << 8 | first-of-state << 15, and
@@ -1199,6 +1206,8 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
 
     // FrozenLake family, one action per step (no reset-and-step): the step's table
     // word trans[(s, a)] is read a step ahead (after the previous selection)
+    // (a registered map's reset lands on a start cell the word was not read for: its
+    // variant reads the word in the step)
     constexpr bool TRPF = RLAMD_TRPF && RS == 0 &&
                           (ENV == RL_ENV_FROZEN_LAKE || ENV == RL_ENV_FROZEN_LAKE_EDITED);
     uint32_t wpf = 0;
@@ -1273,11 +1282,11 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
                 doS = alive;
             }
         }
-        if constexpr (ENV == RL_ENV_FROZEN_LAKE || ENV == RL_ENV_FROZEN_LAKE_EDITED) {
+        if constexpr (env_fl_family(ENV)) {
             uint32_t pos = L.s;                    // reset or step in one predicated block
             const uint32_t w = TRPF ? wpf : tabs.trans[tidx<LDS_AM, 4>(tabs, L.s, L.a)];
-            fl_advance<ENV == RL_ENV_FROZEN_LAKE_EDITED, SLIP, LDS_AM>(doR, doS, pos, L.z, w, L.rng, tabs, s2, r,
-                                                                       term);
+            fl_advance<env_fl_edited(ENV), SLIP, LDS_AM, env_map_start(ENV)>(doR, doS, pos, L.z, w, L.rng, tabs, s2,
+                                                                             r, term);
             L.ready = doR ? true : (term ? false : L.ready);
         } else if constexpr (ENV == RL_ENV_BLACKJACK && RLAMD_BJ_ONE_LOOP) {
             E::advance(doR, doS, L.z, L.a, L.rng, s2, r, term);
@@ -2086,7 +2095,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
 template <int ENV, int AGENT, int POLICY>
 constexpr bool use_w() {
     return RLAMD_TRACES_W && AGENT == RL_AGENT_TRACES && POLICY != RL_POLICY_NEURAL &&
-           (ENV == RL_ENV_CLIFF_WALKING || ENV == RL_ENV_FROZEN_LAKE || ENV == RL_ENV_FROZEN_LAKE_EDITED);
+           (ENV == RL_ENV_CLIFF_WALKING || env_fl_family(ENV));
 }
 // the shared kernel for the agent's representation (nullptr: the fixed point
 // cannot be proven for this variant, so the host never asks for it)
@@ -2154,7 +2163,7 @@ const void *o8_kernel(const KParams &p) {
 }
 template <int ENV, int AGENT, int POLICY, int SEL, int ALGO>
 constexpr bool use_o8() {
-    return ((ENV == RL_ENV_FROZEN_LAKE || ENV == RL_ENV_CLIFF_WALKING) && AGENT == RL_AGENT_ONE_STEP &&
+    return ((env_fl_plain(ENV) || ENV == RL_ENV_CLIFF_WALKING) && AGENT == RL_AGENT_ONE_STEP &&
             POLICY == RL_POLICY_TABULAR && !(SEL == RL_SEL_UCB && ALGO == RL_ALGO_EXPECTED_SARSA)) ||
            // Blackjack eps-greedy (compact rows: <= 35 KiB per group of 512, four groups
            // per CU): 67 VGPRs at the default bound left it at 3 groups per CU, i.e. a
@@ -2256,7 +2265,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 // (and launch_train) also require the bin's shape and activations at run time
 template <int ENV, int AGENT, int POLICY>
 __host__ __device__ constexpr bool use_net_regs() {
-    return RLAMD_NET_REGS && POLICY == RL_POLICY_NEURAL && AGENT == RL_AGENT_ONE_STEP && ENV == RL_ENV_FROZEN_LAKE;
+    return RLAMD_NET_REGS && POLICY == RL_POLICY_NEURAL && AGENT == RL_AGENT_ONE_STEP && env_fl_plain(ENV);
 }
 
 // Private agents with small tables (KParams::priv_lpw != 0; FrozenLake 4x4 / 8x8,

@@ -98,6 +98,8 @@ SIGNATURES = {
     "rl_device_count": (C.c_int, [_P(C.c_int)]),
     "rl_blackjack_obs_id": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "rl_obs_to_reference": (C.c_uint64, [C.c_int32, C.c_uint32]),
+    "rl_map_register": (C.c_int, [_P(C.c_char_p), C.c_uint32, _P(C.c_int32)]),
+    "rl_map_info": (C.c_int, [C.c_int32, _P(C.c_uint32), _P(C.c_uint32), _V, C.c_size_t]),
     "rl_env_dims": (C.c_int, [_P(EnvConfig), _P(C.c_uint32), _P(C.c_uint32)]),
     "rl_env_table": (C.c_int, [_P(EnvConfig), _V, _V, _V, _V, _V]),
     "rl_env_create": (C.c_int, [_P(EnvConfig), C.c_uint32, C.c_uint64, C.c_uint64, C.c_int32, _P(_V)]),
@@ -219,8 +221,36 @@ def env_config(p):
     return c
 
 
+MAP_MAX_CELLS = 64    # rl.h RL_MAP_MAX_CELLS
+
+
+def register_map(rows):
+    """FrozenLakeEnv::new / FrozenLakeEditedEnv::new with the caller's map (rl.h
+    rl_map_register): rows of equal length over S, F, H, G.  Returns the id to put in
+    `map8x8` (>= 2; the same rows give the same id again)."""
+    rows = [r.encode() if isinstance(r, str) else bytes(r) for r in rows]
+    arr = (C.c_char_p * max(len(rows), 1))(*rows)
+    mid = C.c_int32(-1)
+    check(lib().rl_map_register(arr, len(rows), C.byref(mid)))
+    return mid.value
+
+
+def map_info(map_id):
+    """The rows of a map id (0 / 1: MAP_4X4 / MAP_8X8), as a list of str"""
+    nr, nc = C.c_uint32(), C.c_uint32()
+    check(lib().rl_map_info(map_id, C.byref(nr), C.byref(nc), None, 0))
+    buf = C.create_string_buffer(nr.value * nc.value)
+    check(lib().rl_map_info(map_id, C.byref(nr), C.byref(nc), buf, nr.value * nc.value))
+    cells = buf.raw.decode()
+    return [cells[r * nc.value:(r + 1) * nc.value] for r in range(nr.value)]
+
+
 def default_params(**kw):
-    """Reference CLI defaults (src/bin/frozen_lake.rs:35-73; decay rule :84)."""
+    """Reference CLI defaults (src/bin/frozen_lake.rs:35-73; decay rule :84).
+    map=rows registers the caller's FrozenLake map and sets its id in `map8x8`."""
+    if "map" in kw:
+        kw = dict(kw)
+        kw["map8x8"] = register_map(kw.pop("map"))
     p = dict(env="frozen_lake", map8x8=0, slippery=0, max_steps=100, agent="one_step",
              policy="tabular", selector="eps_greedy", algo="qlearning", decay_kind=0,
              lr=0.05, gamma=0.95, lambda_=0.5, eps0=1.0, n_episodes_for_decay=100000,
