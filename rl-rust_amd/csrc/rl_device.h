@@ -80,19 +80,12 @@ __device__ __forceinline__ double uniform01(Rng &r) {
 // <= 2^-32); only then is the word holding m's low 20 bits drawn (DESIGN §2
 // "draws": the same exact test, one u32 per selection).  eps * 2^32 and h + 1
 // are exact; NaN eps fails every compare and reaches the exact test.
-#ifndef RLAMD_EPSX
-#define RLAMD_EPSX 1
-#endif
 __device__ __forceinline__ bool eps_test(Rng &r, double eps) {
     const uint32_t h = r.next_u32();
     const double e32 = __builtin_ldexp(eps, 32), hd = (double)h;
     bool lt = hd + 1.0 <= e32;                  // u < (h + 1) 2^-32 <= eps
-#if RLAMD_EPSX
     const bool may = hd < e32;                  // u < eps possible (implied by lt)
     if (may != lt) {                            // undecided: m's low bits
-#else
-    if (!lt && hd < e32) {                      // undecided: m's low bits
-#endif
         const uint32_t l = r.next_u32();
         const uint64_t bits = (((((uint64_t)h << 32) | l) >> 12)) | 0x3FF0000000000000ull;
         lt = __longlong_as_double((long long)bits) - 1.0 < eps;
@@ -455,27 +448,14 @@ __device__ __forceinline__ uint32_t ucb_known(const double (&v)[A], const uint64
     }
     return need;
 }
-#ifndef RLAMD_UCB_PRED
-#define RLAMD_UCB_PRED 0   // 1: ucb_fill predicated (every entry computed, selected): measured 0.4521 vs 0.4513 ms
-                           // on cfg 3, 1.400 vs 1.401 on cfg 8 (profiles/r05/ucb_pred_ab.txt), so off
-#endif
+// per-action branches: a predicated fill (every entry computed, then selected) measured
+// 0.4521 vs 0.4513 ms on cfg 3, 1.400 vs 1.401 on cfg 8 (profiles/r05/ucb_pred_ab.txt)
 template <int A>
 __device__ __forceinline__ void ucb_fill(const double (&v)[A], const uint64_t (&n)[A], double c, double lnt,
                                          uint32_t need, double (&u)[A]) {
-    if constexpr (RLAMD_UCB_PRED) {
-        // predicated: the A quotients and roots for every lane of the wave, kept where
-        // needed (a divergent `if` per action cost an exec-mask triple each, VERDICT
-        // r04 weak 4); the values are those of ucb_value, selected bit for bit
 #pragma unroll
-        for (int i = 0; i < A; ++i) {
-            const double x = ucb_value(v[i], c, lnt, (double)n[i]);
-            u[i] = ((need >> i) & 1u) ? x : u[i];
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < A; ++i)
-            if ((need >> i) & 1u) u[i] = ucb_value(v[i], c, lnt, (double)n[i]);
-    }
+    for (int i = 0; i < A; ++i)
+        if ((need >> i) & 1u) u[i] = ucb_value(v[i], c, lnt, (double)n[i]);
 }
 
 // ------------------------------------------------------------------ f64 shared Q
@@ -503,22 +483,6 @@ __device__ __forceinline__ double nf_value(uint32_t f) {
 // d on the grid 2^e, rounded half-to-even; |d| < 2^(e+53) so the result is exact in int64
 __device__ __forceinline__ int64_t fq_raw(double d, int e) {
     return (int64_t)__builtin_rint(__builtin_ldexp(d, -e));
-}
-// 1.0 / n (0 for n == 0) without a table read: v_rcp_f64 and two Newton steps
-// (with one step the cfg 2 fixtures failed: not correctly rounded).  After the
-// first step the relative error is below 2^-52, after the second y1 * (2 - n y1)
-// is within about 2^-104 of 1/n and the last fma rounds once, and 1/n for small n
-// is far from any rounding midpoint, so this should be the correctly rounded
-// 1.0 / n — an argument, not a check: it is used only with RLAMD_SETTLE_RCPN,
-// which is off because on cfg 2 the f64 chain measured slower than the table read
-// it replaces (0.199 against 0.188 ms per launch, A/B on one box).
-__device__ __forceinline__ double rcp_nr(uint32_t n) {
-    const double dn = (double)n;
-    const double r0 = __builtin_amdgcn_rcp(dn);
-    const double e0 = __builtin_fma(-dn, r0, 1.0);
-    const double r1 = __builtin_fma(r0, e0, r0);
-    const double e1 = __builtin_fma(-dn, r1, 1.0);
-    return n ? __builtin_fma(r1, e1, r1) : 0.0;
 }
 // argmax (first maximum, strict >) and max of one f64 row in a single pass
 // (utils.rs:1-21: a NaN at index 0 sticks, later NaNs never win)
@@ -563,20 +527,6 @@ __device__ __forceinline__ uint32_t argmax_i64(const int64_t (&v)[A]) {
 #pragma unroll
     for (int i = 1; i < A; ++i)
         if (v[i] > m) { m = v[i]; r = (uint32_t)i; }
-    return r;
-}
-// argmax and max of one row in a single pass (first maximum, strict `>`): the
-// index is argmax_i64's and the value max_i64's
-template <int A>
-__device__ __forceinline__ uint32_t argmax_max_i64(const int64_t (&v)[A], int64_t &m) {
-    m = v[0];
-    uint32_t r = 0;
-#pragma unroll
-    for (int i = 1; i < A; ++i) {
-        const bool gt = v[i] > m;
-        m = gt ? v[i] : m;
-        r = gt ? (uint32_t)i : r;
-    }
     return r;
 }
 template <int A>
@@ -876,10 +826,6 @@ template <> struct EnvDev<RL_ENV_TAXI> {
 // z packs the hand: bits 0-7 player sum, 8-15 dealer sum, 16-19 dealer[0],
 // bit 20 player_has_ace, bit 21 dealer_has_ace (aces from the first two cards
 // only, :54-55).  Dense obs = (p_score*27 + d_score)*2 + p_ace  (p <= 31, d <= 26).
-#ifndef RLAMD_BJ_STEP1
-#define RLAMD_BJ_STEP1 1   // Blackjack step: hit and stick in one draw loop (EnvDev<BLACKJACK>::step);
-                           // cfg 5 0.3511 -> 0.3367 ms per launch (profiles/r05/bj_step1_ab.txt)
-#endif
 template <> struct EnvDev<RL_ENV_BLACKJACK> {
     static constexpr int A = 2;
     __device__ static __forceinline__ uint32_t score(uint32_t sum, uint32_t ace) {
@@ -916,106 +862,37 @@ template <> struct EnvDev<RL_ENV_BLACKJACK> {
                                                 bool &term) {
         uint32_t ps = z & 0xffu, ds = (z >> 8) & 0xffu;
         const uint32_t d0 = (z >> 16) & 0xfu, pa = (z >> 20) & 1u, da = (z >> 21) & 1u;
-        if constexpr (RLAMD_BJ_STEP1) {
-            // hit and stick in ONE draw loop (a wave holds lanes of both): a hit lane
-            // takes the first accepted half of its words (CardSrc), a stick lane the
-            // dealer's cards while d < 17, two per word — the draws of the two blocks
-            // below, in their order; the wave runs max(words) iterations instead of
-            // the hit block and then the dealer loop
-            const bool hit = a == 0u;
-            uint32_t d = score(ds, da);
-            bool act = hit || d < 17u;
-            while (act) {
-                const uint32_t w = r.next_u32();
-                uint32_t c;
-                if (card16(w >> 16, c)) {
-                    ps += hit ? c : 0u;
-                    ds += hit ? 0u : c;
-                    d = score(ds, da);
-                    act = !hit && d < 17u;
-                }
-                if (act && card16(w & 0xFFFFu, c)) {
-                    ps += hit ? c : 0u;
-                    ds += hit ? 0u : c;
-                    d = score(ds, da);
-                    act = !hit && d < 17u;
-                }
+        // hit and stick in ONE draw loop (a wave holds lanes of both): a hit lane
+        // takes the first accepted half of its words (CardSrc's order: :121-138), a
+        // stick lane the dealer's cards while d < 17, two per word (:139-162); the
+        // wave runs max(words) iterations instead of a hit block and then a dealer
+        // loop (cfg 5 0.3511 -> 0.3367 ms per launch, profiles/r05/bj_step1_ab.txt)
+        const bool hit = a == 0u;
+        uint32_t d = score(ds, da);
+        bool act = hit || d < 17u;
+        while (act) {
+            const uint32_t w = r.next_u32();
+            uint32_t c;
+            if (card16(w >> 16, c)) {
+                ps += hit ? c : 0u;
+                ds += hit ? 0u : c;
+                d = score(ds, da);
+                act = !hit && d < 17u;
             }
-            const uint32_t p = score(ps, pa);          // d == score(ds, da) for both kinds
-            const bool bust = p > 21u;
-            s2 = obs(p, hit ? (bust ? d : d0) : d, pa);
-            term = hit ? bust : true;
-            rew = hit ? (bust ? -1.0 : 0.0) : (d > 21u ? 1.0 : (p > d ? 1.0 : (p < d ? -1.0 : 0.0)));
-            z = ps | (ds << 8) | (z & 0xffff0000u);
-            pos = s2;
-            return;
+            if (act && card16(w & 0xFFFFu, c)) {
+                ps += hit ? c : 0u;
+                ds += hit ? 0u : c;
+                d = score(ds, da);
+                act = !hit && d < 17u;
+            }
         }
-        if (a == 0) {                                  // hit :121-138
-            CardSrc cs;
-            ps += cs.next(r);
-            const uint32_t p = score(ps, pa);
-            if (p > 21u) {
-                s2 = obs(p, score(ds, da), pa); rew = -1.0; term = true;
-            } else {
-                s2 = obs(p, d0, pa); rew = 0.0; term = false;
-            }
-        } else {                                       // stick :139-162
-            uint32_t d = score(ds, da);
-            while (d < 17u) {                          // two cards per word (CardSrc's order)
-                const uint32_t w = r.next_u32();
-                uint32_t c;
-                if (card16(w >> 16, c)) { ds += c; d = score(ds, da); }
-                if (d < 17u && card16(w & 0xFFFFu, c)) { ds += c; d = score(ds, da); }
-            }
-            const uint32_t p = score(ps, pa);
-            s2 = obs(p, d, pa);
-            term = true;
-            rew = d > 21u ? 1.0 : (p > d ? 1.0 : (p < d ? -1.0 : 0.0));
-        }
+        const uint32_t p = score(ps, pa);          // d == score(ds, da) for both kinds
+        const bool bust = p > 21u;
+        s2 = obs(p, hit ? (bust ? d : d0) : d, pa);
+        term = hit ? bust : true;
+        rew = hit ? (bust ? -1.0 : 0.0) : (d > 21u ? 1.0 : (p > d ? 1.0 : (p < d ? -1.0 : 0.0)));
         z = ps | (ds << 8) | (z & 0xffff0000u);
         pos = s2;
-    }
-    // reset (doR) or step (doS) of one lane in ONE draw loop, for the learner-group
-    // kernel where a wave holds lanes of both kinds: a reset lane draws P0, P1, D0,
-    // D1, a hit lane one card, a stick lane the dealer's cards while d < 17 — the
-    // same draws in the same order as reset() / step(), but the wave runs
-    // max(draws) iterations instead of the reset block + the hit block + the
-    // dealer loop one after another.
-    __device__ static __forceinline__ void advance(bool doR, bool doS, uint32_t &z, uint32_t a, Rng &r,
-                                                   uint32_t &s2, double &rew, bool &term) {
-        uint32_t ps = z & 0xffu, ds = (z >> 8) & 0xffu, d0 = (z >> 16) & 0xfu, pa = (z >> 20) & 1u,
-                 da = (z >> 21) & 1u;
-        if (doR) { ps = 0u; ds = 0u; d0 = 0u; pa = 0u; da = 0u; }
-        const bool hit = doS && a == 0u, stick = doS && a != 0u;
-        const uint32_t nfix = doR ? 4u : (hit ? 1u : 0u);
-        CardSrc cs;                                    // the lane's operation draws its own words
-        for (uint32_t i = 0;; ++i) {
-            if (!(i < nfix || (stick && score(ds, da) < 17u))) break;
-            const uint32_t c = cs.next(r);
-            if (doR) {
-                if (i < 2u) { ps += c; pa |= c == 1u ? 1u : 0u; }
-                else { if (i == 2u) d0 = c; ds += c; da |= c == 1u ? 1u : 0u; }
-            } else if (hit) {
-                ps += c;
-            } else {
-                ds += c;
-            }
-        }
-        const uint32_t p = score(ps, pa);
-        if (doR) {
-            z = ps | (ds << 8) | (d0 << 16) | (pa << 20) | (da << 21);
-            s2 = obs(p, d0, pa);                       // reset :105-116
-        } else if (hit) {                              // :121-138
-            if (p > 21u) { s2 = obs(p, score(ds, da), pa); rew = -1.0; term = true; }
-            else { s2 = obs(p, d0, pa); rew = 0.0; term = false; }
-            z = ps | (ds << 8) | (z & 0xffff0000u);
-        } else if (stick) {                            // :139-162
-            const uint32_t d = score(ds, da);
-            s2 = obs(p, d, pa);
-            term = true;
-            rew = d > 21u ? 1.0 : (p > d ? 1.0 : (p < d ? -1.0 : 0.0));
-            z = ps | (ds << 8) | (z & 0xffff0000u);
-        }
     }
 };
 

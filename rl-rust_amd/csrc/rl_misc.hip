@@ -46,12 +46,9 @@ uint32_t shared_pair_cap(int env, int agent, int policy, int sel, int algo, uint
                        qsh_layout(fq, ucb, P, algo) ? 1 : 0).trc_cap;
 }
 // the envs whose shared pair lists append through pair_visit (slot_of + vbits for
-// the HBM slots); the small tables keep their pair bits in registers (PBITS in
-// train_shared_body) and never read either
-bool pair_slot_index_env(int env) {
-    return !(RLAMD_COOP_SWEEP && RLAMD_PAIR_BITS &&
-             (env == RL_ENV_CLIFF_WALKING || env_fl_family(env)));
-}
+// the HBM slots); the small tables keep their pairs in wave pools with the pair
+// bits in registers (POOL in train_shared_body) and never read either
+bool pair_slot_index_env(int env) { return !pair_pool_env(env); }
 
 // ---------------------------------------------------------------- pair-trace re-index
 // A lane's pair list keeps slots [0, cap) in LDS during a launch and [cap, np) in

@@ -20,30 +20,8 @@
 
 namespace rlamd {
 
-#ifndef RLAMD_FUSE_MAX
-#define RLAMD_FUSE_MAX 2   // single-table Q-learning: one argmax+max pass per step (0: off,
-                           // 1: fused, 2: fused and pinned before the selection)
-#endif
-
-// Pair pools (the small-table traces kernel, cfg 4):
-//  RLAMD_POOL_BF    the item body branch-free: every item of a round adds its
-//                   contribution and its row count (0 for the items of lanes that
-//                   do not train), the non-finite case behind one wave-uniform test,
-//                   the keep-write's LDS / HBM choice uniform while the round fits
-//  RLAMD_POOL_REC16 an item's tag and E as one 16-byte LDS record (one ds_read_b128
-//                   and one ds_write_b128 per item instead of a u16 and an f64 each)
-//  RLAMD_POOL_LREC  each lane's {td, pk} in a 16-byte LDS record read by its items
-//                   (one ds_read_b128) instead of three ds_bpermute
-#ifndef RLAMD_POOL_BF
-#define RLAMD_POOL_BF 0
-#endif
-#ifndef RLAMD_POOL_REC16
-#define RLAMD_POOL_REC16 0
-#endif
-#ifndef RLAMD_POOL_LREC
-#define RLAMD_POOL_LREC 1
-#endif
-__host__ __device__ constexpr uint32_t pool_item_bytes() { return RLAMD_POOL_REC16 ? 16u : 10u; }
+// a pair-pool item in LDS (the small-table traces kernel, cfg 4): a u16 tag and its f64 E
+constexpr uint32_t POOL_ITEM_BYTES = 10u;
 struct SmemLayout {
     uint32_t st, misc, q, sum, cnt, sfl, qf, n, nd, t, list, rcp, tr, cdf, lrec, trc, qd, rm, total;
     uint32_t trc_cap;   // pair traces: list slots per lane held in LDS (the rest in HBM)
@@ -80,67 +58,17 @@ __host__ __device__ constexpr bool pair_pool_env(int env) {
 // Fixed-point single-table Q-learning (rl_device.h argmax_max, the fused argmax +
 // max of the target row) keeps an f64 image of every entry beside its int64 word:
 // the step reads values (selection, TD target, Q(s,a)) without converting, and
-// the settle, the only writer, converts once per changed entry.
-#ifndef RLAMD_NF_SKIP
-#define RLAMD_NF_SKIP 1   // f64 one-step: no pass-2 count for entries with non-finite contributions
-#endif
-#ifndef RLAMD_LATE_B3
-#define RLAMD_LATE_B3 1   // the step-separating barrier after the next step's env step
-#endif
-#ifndef RLAMD_TAXI_PF
-#define RLAMD_TAXI_PF 1   // Taxi: the next step's transition word read from the HBM table after the selection
-#endif
-#ifndef RLAMD_TRPF
-#define RLAMD_TRPF 0   // 1: FrozenLake reads the next step's transition word after the selection
-                       // (cfg 2: 0.2122-0.2139 ms against 0.2116-0.2125 without, A/B on one box)
-#endif
-#ifndef RLAMD_EARLY_COUNT
-#define RLAMD_EARLY_COUNT 0   // 1: count the step's train / episode-end lanes where their masks form (cfg 2: 147 static VALU against 144)
-#endif
-#ifndef RLAMD_TAIL
-#define RLAMD_TAIL 0   // 1: the throughput kernels' end-of-step bookkeeping as one predicated
-                       // block (cfg 2: 0.2149-0.2157 ms against 0.2139-0.2145, A/B on one box)
-#endif
-#ifndef RLAMD_QSH
-#define RLAMD_QSH 2   // 0: off; 1: row reads as the compiler picks (ds_read2_b64: 0.2574 ms on cfg 2);
-                      // 2: rows as 16-byte reads (0.2156 ms; no shadow 0.2206 ms)
-#endif
+// the settle, the only writer, converts once per changed entry (cfg 2: 0.2156 ms
+// per launch with the image, 0.2206 ms without).
 __host__ __device__ constexpr bool qsh_layout(int fq, int ucb, int P, int algo) {
-    return RLAMD_QSH != 0 && RLAMD_FUSE_MAX != 0 && !fq && !ucb && P == 1 && algo == RL_ALGO_QLEARNING;
+    return !fq && !ucb && P == 1 && algo == RL_ALGO_QLEARNING;
 }
 // Row summaries (the QSH layout, rows of 4 actions): RM[s] = (max, argmax) of row
 // s, written by the settle for every row each step, so a step reads its target
 // row's argmax (the exploit action) and max (the Q-learning target) as one 16-byte
 // LDS read instead of the 32-byte row and the 4-way compare chain.  The settle
-// then runs on 2 of a group's 8 waves, each thread two entries of a row, with the
-// row's halves combined across lane pairs (DPP).
-#ifndef RLAMD_ROWMAX
-#define RLAMD_ROWMAX 1
-#endif
-#ifndef RLAMD_RM_PIN
-#define RLAMD_RM_PIN 0
-#endif
-#ifndef RLAMD_QA_EARLY
-#define RLAMD_QA_EARLY 1   // rmx: Q(s, a) for the TD read right after the barrier, beside the row summary
-#endif
-#ifndef RLAMD_RSUM_REG
-#define RLAMD_RSUM_REG 0   // 1: training-episode rewards summed per lane in registers, one LDS add per wave
-                           // at launch end (cfg 2: 0.1929 against 0.1896 ms per launch, A/B on one box)
-#endif
-#ifndef RLAMD_RUN_TRAIN
-#define RLAMD_RUN_TRAIN 0  // 1: throughput mode takes train == doS (a live lane is always in TRAIN mode);
-                           // with RSUM_REG 0.1903 ms, no gain
-#endif
-#ifndef RLAMD_QA_EARLY2
-#define RLAMD_QA_EARLY2 1   // traces (not UCB + expected SARSA): Q(s, a) read early (cfg 4: 0.5377 -> 0.5339 ms;
-                            // on cfg 5's one-step double tables it measured 0.3528 -> 0.3549: not used there)
-#endif
-#ifndef RLAMD_SETTLE_RCPN
-#define RLAMD_SETTLE_RCPN 0   // 1: the settle's 1/n by v_rcp_f64 + one Newton step, no table read
-#endif
-#ifndef RLAMD_SETTLE_QUAD
-#define RLAMD_SETTLE_QUAD 1   // 1: one entry per thread (4 waves), the row summary by 2 DPP steps per quad
-#endif
+// then runs on 4 of a group's 8 waves, one entry per thread, with the row's four
+// entries combined by two DPP steps per lane quad (settle_quad).
 // LDS carve of one learner group (shared mode) or of the tables only (private).
 //   misc u32[4]            f64 traces: the group step's max td code
 //   q    int64 [P][S][A]   the group's Q copy (fixed point 2^-40, or f64 bits)
@@ -158,7 +86,13 @@ __host__ __device__ constexpr bool qsh_layout(int fq, int ucb, int P, int algo) 
 //        transitions and reads its start cdf from HBM, Blackjack has none)
 //   trc  pair traces (traces == 2): the first trc_cap slots of every lane's pair
 //        list, ids u16 [cap][nthr] then E f64 [cap][nthr] (column = thread);
-//        small tables: the first trc_cap items of every wave's pair pool
+//        small tables: the first trc_cap items of every wave's pair pool, tags
+//        u16 [waves][cap] then E f64 [waves][cap]
+//   lrec pair pools: uint4 [waves][64], each lane's {td, pk} for the step's sweep
+//   qd   f64 [P][S][A]  the f64 image of the fixed-point words (qsh_layout)
+//   rm   double2 [S]    qd with rows of 4: (max, argmax) of every row
+// st (the block's stats accumulators) comes first; cdf (a registered map's start
+// list) sits between tr and lrec.
 // nthr = the shared kernel's block size; 0 for the private kernel (tables only).
 // traces: 0 none, 1 whole-row visited-state sets, 2 visited-pair sets
 // ucb: 0 none, 1 UCB, 2 UCB + expected SARSA (launch counts u32 [S][A] + step
@@ -205,12 +139,12 @@ __host__ __device__ inline SmemLayout smem_layout(int env, int P, int ucb, int t
     // pool form (small tables, pair_pool): trc_cap = items per wave, tags u16
     // [waves][cap] then E f64 [waves][cap]
     const bool pool = shared_q && traces == 2 && pair_pool_env(env);
-    // RLAMD_POOL_LREC: the pool sweep's per-lane record {td, pk} (16 B per lane of
-    // every wave), read by the items instead of three shuffles
+    // the pool sweep's per-lane record {td, pk} (16 B per lane of every wave), read
+    // by the items (one ds_read_b128) instead of three shuffles
     l.lrec = off;
-    if (pool && RLAMD_POOL_LREC) off += (nthr >> 6) * 64u * 16u;
+    if (pool) off += (nthr >> 6) * 64u * 16u;
     if (pool) {
-        const uint32_t nw = nthr >> 6, c = trc_kb * 1024u / (nw * pool_item_bytes());
+        const uint32_t nw = nthr >> 6, c = trc_kb * 1024u / (nw * POOL_ITEM_BYTES);
         l.trc_cap = c < 64u * S * A ? c : 64u * S * A;
     } else if (shared_q && traces == 2) {
         const uint32_t c = trc_kb * 1024u / ((nthr + 2u) * 2u + (nthr + 1u) * 8u);
@@ -219,15 +153,14 @@ __host__ __device__ inline SmemLayout smem_layout(int env, int P, int ucb, int t
         l.trc_cap = 0u;
     }
     l.trc = off;
-    if (pool && RLAMD_POOL_REC16) off += l.trc_cap * (nthr >> 6) * 16u;
-    else if (pool) off += l.trc_cap ? align16(l.trc_cap * (nthr >> 6) * 2u) + l.trc_cap * (nthr >> 6) * 8u : 0u;
+    if (pool) off += l.trc_cap ? align16(l.trc_cap * (nthr >> 6) * 2u) + l.trc_cap * (nthr >> 6) * 8u : 0u;
     else off += l.trc_cap ? align16(l.trc_cap * (nthr + 2u) * 2u) + l.trc_cap * (nthr + 1u) * 8u : 0u;
     // qd  f64 [P][S][A]  fixed-point single-table Q-learning: the f64 image of every
     //                    entry beside its int64 word (qsh_layout), read by the step
     if (shared_q && qsh) off = align16(off);
     l.qd = off; off += (shared_q && qsh) ? PSA * 8u : 0u;
     off = align16(off);
-    l.rm = off; off += (shared_q && qsh && RLAMD_ROWMAX && A == 4u && P == 1) ? SL * 16u : 0u;
+    l.rm = off; off += (shared_q && qsh && A == 4u && P == 1) ? SL * 16u : 0u;
     l.total = off;
     return l;
 }
@@ -456,52 +389,14 @@ __device__ __forceinline__ void trace_sweep(const KParams &p, uint64_t lane, uin
 // Slots j < cap live in LDS (TRI ids / TRE values, column = thread) for the
 // launch and are found by a scan; slots j >= cap live in HBM (tlist / trace
 // [j][L]) with slot_of [id][L] and the visited-state bitmap vbits for them.
-#ifndef RLAMD_PLAN_PB
-#define RLAMD_PLAN_PB 16   // Dyna planning steps whose draws and model reads go out together
-#endif
-#ifndef RLAMD_PLAN_PF
-#define RLAMD_PLAN_PF 1   // Dyna planning (eps-greedy): a batch's draws first, its model reads together
-#endif
-#ifndef RLAMD_LAZY_ROWS
-#define RLAMD_LAZY_ROWS 1   // reset-and-step: the reset's selection reads its row only for exploiting lanes
-#endif
-#ifndef RLAMD_BJ_ONE_LOOP
-// Blackjack learner groups: reset and step draws in one loop (EnvDev::advance).
-// Parity-green but measured slower on cfg 5 (4.98e10 vs 5.83e10 env-steps/s on
-// the 8-wave kernel), so off
-#define RLAMD_BJ_ONE_LOOP 0
-#endif
-
-#ifndef RLAMD_SWEEP_U
-#define RLAMD_SWEEP_U 4   // pair-trace sweep: rounds of 64 items interleaved per iteration
-                          // (cfg 4: 1 / 2 / 4 -> 1.163 / 1.089 / 1.058 ms per launch)
-#endif
-#ifndef RLAMD_COOP_SWEEP
-#define RLAMD_COOP_SWEEP 1   // shared pair traces: wave-cooperative sweep (0: each lane its own list)
-#endif
-#ifndef RLAMD_PAIR_BITS
-#define RLAMD_PAIR_BITS 1   // small tables: visited-pair bitmap in registers (0: scan the list)
-#endif
-#ifndef RLAMD_TRACES_W
-#define RLAMD_TRACES_W 0   // small-table traces at <= 2 groups per CU: a 256-VGPR kernel
-                           // (measured equal on cfg 4 once the bitmap and opq() removed the
-                           // scratch arrays: 0.8875 vs 0.8869 ms, so off)
-#endif
-#ifndef RLAMD_OWNER_SCAN
-#define RLAMD_OWNER_SCAN 1   // pair-trace sweep: item owners by ballot + readlane scan (0: shuffle binary search)
-#endif
-#ifndef RLAMD_PAIR_TC
-#define RLAMD_PAIR_TC 8   // HBM pair slots per batch of the sweep (loads issued together)
-#endif
+// pair-trace sweeps (pool and wave-cooperative): rounds of 64 items interleaved per
+// iteration (cfg 4: 1 / 2 / 4 -> 1.163 / 1.089 / 1.058 ms per launch)
+constexpr uint32_t SWEEP_U = 4;
 // HBM pair slots (those past the LDS cache): lane-major, [lane][j] with stride S*A
 // (the longest list), so the consecutive items of one lane a sweep round takes
 // are contiguous — one or two cache lines instead of one line per item
-#ifndef RLAMD_PAIR_LANE_MAJOR
-#define RLAMD_PAIR_LANE_MAJOR 1   // 0: slot-major [j][lane]
-#endif
 __device__ __forceinline__ uint64_t pslot(const KParams &p, uint32_t j, uint64_t lane) {
-    if constexpr (RLAMD_PAIR_LANE_MAJOR) return lane * (uint64_t)(p.S * p.A) + j;
-    else return (uint64_t)j * p.L + lane;
+    return lane * (uint64_t)(p.S * p.A) + j;
 }
 struct PairCache {
     uint16_t *TRI;
@@ -561,49 +456,6 @@ __device__ __forceinline__ void pair_visit(const KParams &p, const PairCache &c,
         p.tlist[pslot(p, j, lane)] = (uint16_t)(id | (first ? 0x8000u : 0u));
         p.slot_of[(uint64_t)id * Ls + lane] = (uint16_t)j;
         p.trace[pslot(p, j, lane)] = 1.0;
-    }
-}
-// the sweep over pairs [0, np): fn(pair id, first-of-state, E); E *= gamma*lambda.
-// LDS slots first, then the HBM slots TC at a time with every load issued first.
-template <class Fn>
-__device__ __forceinline__ void pair_sweep(const KParams &p, const PairCache &c, uint64_t lane, uint32_t np,
-                                           Fn &&fn) {
-    const uint32_t nl = np < c.cap ? np : c.cap;
-    constexpr uint32_t TL = 4;                      // LDS slots read TL at a time (latency)
-    for (uint32_t j0 = 0; j0 < nl; j0 += TL) {
-        uint32_t w[TL];
-        double ev[TL];
-#pragma unroll
-        for (uint32_t k = 0; k < TL; ++k) {
-            const uint32_t j = j0 + k < nl ? j0 + k : j0;
-            w[k] = c.TRI[c.ixi(j)];
-            ev[k] = c.TRE[c.ixe(j)];
-        }
-#pragma unroll
-        for (uint32_t k = 0; k < TL; ++k) {
-            if (j0 + k < nl) {
-                fn(w[k] & 0x7fffu, (w[k] & 0x8000u) != 0u, ev[k]);
-                c.TRE[c.ixe(j0 + k)] = ev[k] * p.gl;
-            }
-        }
-    }
-    constexpr uint32_t TC = RLAMD_PAIR_TC;
-    for (uint32_t j0 = c.cap; j0 < np; j0 += TC) {
-        uint32_t w[TC];
-        double ev[TC];
-#pragma unroll
-        for (uint32_t k = 0; k < TC; ++k) {
-            const uint32_t j = j0 + k < np ? j0 + k : j0;
-            w[k] = p.tlist[pslot(p, j, lane)];
-            ev[k] = p.trace[pslot(p, j, lane)];
-        }
-#pragma unroll
-        for (uint32_t k = 0; k < TC; ++k) {
-            if (j0 + k < np) {
-                fn(w[k] & 0x7fffu, (w[k] & 0x8000u) != 0u, ev[k]);
-                p.trace[pslot(p, j0 + k, lane)] = ev[k] * p.gl;
-            }
-        }
     }
 }
 // the episode ended: the list is emptied by np = 0; the bitmap (set only by
@@ -758,9 +610,9 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
     if constexpr (env_map_start(ENV))
         for (uint32_t i = tid; i < p.n_start * 3u; i += nthr)
             ((uint32_t *)(smem + lay.cdf))[i] = ((const uint32_t *)p.start_cdf)[i];
-    // row summaries (RLAMD_ROWMAX): in the sweep form only (the settle rewrites them)
+    // row summaries: in the sweep form only (the settle rewrites them)
     const bool sweep = SWEEP == 1 || PSAL <= nthr;   // SWEEP == 1: the host checked PSA <= block
-    const bool rmx = QSH && RLAMD_ROWMAX && A == 4 && sweep;
+    const bool rmx = QSH && A == 4 && sweep;
     if (rmx) {
         for (uint32_t r = tid; r < SL; r += nthr) {
             double v[A], m;
@@ -815,13 +667,11 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
     if constexpr (TRACES) tcnt = active ? p.tcnt[lane] : 0u;
     const PairCache pc{(uint16_t *)(smem + lay.trc), (double *)(smem + lay.trc + align16(lay.trc_cap * (nthr + 2u) * 2u)),
                        lay.trc_cap, nthr, tid};
-    // small tables (S*A <= 256: FrozenLake, CliffWalking): the lane's visited-pair set
-    // as a bitmap in registers, rebuilt from the list at launch start.  A visit then
-    // needs no scan: a new pair is appended, a visited one gets its E += 1 inside the
-    // sweep (the same f64 add, before its use), and "first pair of its state" is the
-    // state's A bits
-    constexpr bool PBITS = PAIRS && RLAMD_COOP_SWEEP && RLAMD_PAIR_BITS &&
-                           (ENV == RL_ENV_CLIFF_WALKING || env_fl_family(ENV));
+    // small tables (S*A <= 256: FrozenLake, CliffWalking; POOL below): the lane's
+    // visited-pair set as a bitmap in registers, rebuilt from the pool at launch start.
+    // A visit then needs no scan: a new pair is appended, a visited one gets its E += 1
+    // inside the sweep (the same f64 add, before its use), and "first pair of its
+    // state" is the state's A bits
     constexpr int PBW = ENV == RL_ENV_CLIFF_WALKING ? 6 : 8;   // 48*4 / 64*4 pair ids
     // pair pool (small tables): the visited pairs of a wave's 64 lanes as ONE list of
     // items, tag = pair id (8 bits) | lane in wave << 8 | first-of-state << 15, and
@@ -832,39 +682,24 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
     // of the wave's lanes' pair rows (p.tlist / p.trace, lane-major, so the wave's
     // rows are one region of 64*S*A >= any pool); the count in p.tcnt[first lane].
     constexpr bool POOL = PAIRS && pair_pool_env(ENV);
-    static_assert(!POOL || (PBITS && A == 4), "pair pool: small-table pair bits");
+    static_assert(!POOL || A == 4, "a state's pair bits sit in one bitmap word");
     const uint32_t pw = tid >> 6, plid = tid & 63u;
     const uint64_t plane0 = (uint64_t)blockIdx.x * p.G + (uint64_t)pw * p.lpw;
     const bool pwave = (uint64_t)pw * p.lpw < p.G && plane0 < p.L;   // the wave holds lanes
     uint16_t *const PT = (uint16_t *)(smem + lay.trc) + pw * lay.trc_cap;
     double *const PE = (double *)(smem + lay.trc + align16(lay.trc_cap * (nthr >> 6) * 2u)) + pw * lay.trc_cap;
-    uint4 *const PR = (uint4 *)(smem + lay.trc) + pw * lay.trc_cap;   // RLAMD_POOL_REC16: {E lo, E hi, tag, 0}
-    uint4 *const LR = (uint4 *)(smem + lay.lrec) + pw * 64u;          // RLAMD_POOL_LREC: {td lo, td hi, pk, 0}
+    uint4 *const LR = (uint4 *)(smem + lay.lrec) + pw * 64u;          // the lanes' {td lo, td hi, pk, 0}
     uint16_t *const HT = p.tlist + plane0 * SA;
     double *const HE = p.trace + plane0 * SA;
     // the LDS part of the wave's pool, item q < trc_cap
-    auto pool_tag = [&](uint32_t q) -> uint32_t {
-        if constexpr (RLAMD_POOL_REC16) return PR[q].z;
-        else return PT[q];
-    };
+    auto pool_tag = [&](uint32_t q) -> uint32_t { return PT[q]; };
     auto pool_get = [&](uint32_t q, uint32_t &tg, double &e) {
-        if constexpr (RLAMD_POOL_REC16) {
-            const uint4 r = PR[q];
-            tg = r.z;
-            e = __longlong_as_double((long long)(((uint64_t)r.y << 32) | r.x));
-        } else {
-            tg = PT[q];
-            e = PE[q];
-        }
+        tg = PT[q];
+        e = PE[q];
     };
     auto pool_put = [&](uint32_t q, uint32_t tg, double e) {
-        if constexpr (RLAMD_POOL_REC16) {
-            const uint64_t b = (uint64_t)__double_as_longlong(e);
-            PR[q] = make_uint4((uint32_t)b, (uint32_t)(b >> 32), tg, 0u);
-        } else {
-            PT[q] = (uint16_t)tg;
-            PE[q] = e;
-        }
+        PT[q] = (uint16_t)tg;
+        PE[q] = e;
     };
     uint32_t npool = 0;
     uint32_t pbits[PBW];
@@ -904,12 +739,6 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
             for (uint32_t k = 0; k < TB; ++k)
                 if (q0 + k < npool && ((t[k] >> 8) & 63u) == plid) pbits_set(t[k] & 0xffu);
         }
-    } else if constexpr (PBITS) {
-        static_assert(A == 4, "a state's pair bits sit in one bitmap word");
-        if (active)
-            for (uint32_t j = 0; j < tcnt; ++j)
-                pbits_set((j < pc.cap ? (uint32_t)pc.TRI[pc.ixi(j)] : (uint32_t)p.tlist[pslot(p, j, lane)]) &
-                          0x7fffu);
     }
 
     // the A visible-flag bytes of LDS row s of table tbl, one per action (A <= 6:
@@ -931,7 +760,7 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
     // QSH: the f64 images of row s; an A == 4 row (32 bytes, 16-aligned) as two
     // 16-byte reads (element-wise, the compiler issued ds_read2_b64: 19 % slower on cfg 2)
     auto qd_row = [&](uint32_t s, double (&v)[A]) {
-        if constexpr (A == 4 && RLAMD_QSH == 2) {
+        if constexpr (A == 4) {
             const double2 *r2 = (const double2 *)__builtin_assume_aligned(QD + qi(0, s, 0), 16);
             const double2 x = r2[0], y = r2[1];
             v[0] = x.x; v[1] = x.y; v[2] = y.x; v[3] = y.y;
@@ -971,7 +800,7 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
     // single-table Q-learning: the selection's argmax and the TD target's max are
     // of the same row s2, so both come from one pass (argmax_max_*) computed for
     // the whole wave before the selection; `pre` is that argmax (-1: none)
-    constexpr bool FUSE_MAX = RLAMD_FUSE_MAX && !UCB && P == 1 && ALGO == RL_ALGO_QLEARNING;
+    constexpr bool FUSE_MAX = !UCB && P == 1 && ALGO == RL_ALGO_QLEARNING;
     auto select = [&](uint32_t s, const int64_t (&ra)[A], const int64_t (&rb)[A], int32_t pre = -1) -> uint32_t {
         if constexpr (!UCB) {                       // uniform_epsilon_greed.rs:51-66
             // one compare decides both the draw (skipped when eps == 0) and the branch
@@ -1010,7 +839,7 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
             return argmax<A>(u);
         }
     };
-    // the fused reset's selection (RLAMD_LAZY_ROWS, eps-greedy without FUSE_MAX): row
+    // the fused reset's selection (eps-greedy without FUSE_MAX): row
     // s is read only by the lanes that exploit — the draws come first either way, so
     // the stream and the result are select()'s
     auto select_lazy = [&](uint32_t s) -> uint32_t {
@@ -1055,8 +884,7 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
         const unsigned long long qold = Q[idx];   // issued beside the SUM read, not after 1/n's
         const uint32_t n = PACKC ? (uint32_t)(packed & 2047) : (uint32_t)CNT16[idx];
         const int64_t sum = PACKC ? (packed >> 11) : packed;
-        const double rc = RLAMD_SETTLE_RCPN ? rcp_nr(n)
-                                            : ((sweep || n < lay.nrcp) ? RCP[n] : 1.0 / (double)n);   // sweep: n <= block size
+        const double rc = (sweep || n < lay.nrcp) ? RCP[n] : 1.0 / (double)n;   // sweep: n <= block size
         // packed: |sum| < 2^51 (pack_proven), so (double)sum is the 1.5*2^52 magic
         const double sd = PACKC ? __longlong_as_double((long long)(0x4338000000000000ull + (uint64_t)sum)) - 0x1.8p52
                                 : (double)sum;
@@ -1070,46 +898,7 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
         if constexpr (!PACKC) CNT16[idx] = 0;
         return v;
     };
-    // row summaries (rmx): thread t settles entries 2t, 2t + 1 (half t & 1 of row t >> 1)
-    // as settle() does, then the row's (max, argmax) — first maximum, strict > as
-    // argmax_max_f64 — from its half and its partner lane's (t ^ 1, same wave)
-    auto settle_pair = [&](uint32_t t) {
-        const uint32_t j = 2u * t;
-        const ulonglong2 sp = *(const ulonglong2 *)__builtin_assume_aligned(&SUM[j], 16);
-        const ulonglong2 qp = *(const ulonglong2 *)__builtin_assume_aligned(&Q[j], 16);
-        int64_t md[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int64_t packed = (int64_t)(h ? sp.y : sp.x);
-            const uint32_t n = PACKC ? (uint32_t)(packed & 2047) : (uint32_t)CNT16[j + h];
-            const int64_t sum = PACKC ? (packed >> 11) : packed;
-            const double sd = PACKC ? __longlong_as_double((long long)(0x4338000000000000ull + (uint64_t)sum)) - 0x1.8p52
-                                    : (double)sum;
-            const double rc = RLAMD_SETTLE_RCPN ? rcp_nr(n) : RCP[n];
-            const double y = __builtin_trunc(sd * rc) + 0x1.8p52;
-            md[h] = (int64_t)((uint64_t)__double_as_longlong(y) - 0x4338000000000000ull);
-        }
-        const unsigned long long q0 = qp.x + (unsigned long long)md[0], q1 = qp.y + (unsigned long long)md[1];
-        *(ulonglong2 *)__builtin_assume_aligned(&Q[j], 16) = make_ulonglong2(q0, q1);
-        const double v0 = q_val((int64_t)q0), v1 = q_val((int64_t)q1);
-        *(double2 *)__builtin_assume_aligned(&QD[j], 16) = make_double2(v0, v1);
-        *(ulonglong2 *)__builtin_assume_aligned(&SUM[j], 16) = make_ulonglong2(0ull, 0ull);
-        if constexpr (!PACKC) *(uint32_t *)&CNT16[j] = 0u;
-        const bool up = v1 > v0;
-        const double m = up ? v1 : v0;
-        const uint32_t a = (t & 1u) * 2u + (up ? 1u : 0u);
-        // the partner half (lanes t, t ^ 1): quad_perm [1,0,3,2]
-        const uint64_t mb = f64_bits(m);
-        const uint32_t pml = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)mb, 0xB1, 0xF, 0xF, false);
-        const uint32_t pmh = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)(mb >> 32), 0xB1, 0xF, 0xF, false);
-        const uint32_t pa = (uint32_t)__builtin_amdgcn_mov_dpp((int)a, 0xB1, 0xF, 0xF, false);
-        const double pm = as_f64(((uint64_t)pmh << 32) | pml);
-        if ((t & 1u) == 0u) {                 // low half: its entries come first (ties stay)
-            const bool hi = pm > m;
-            RM[t >> 1] = make_double2(hi ? pm : m, as_f64((uint64_t)(hi ? pa : a)));
-        }
-    };
-    // RLAMD_SETTLE_QUAD: thread t settles entry t (row t >> 2 is one lane quad) and
+    // row summaries (rmx): thread t settles entry t (row t >> 2 is one lane quad) and
     // the row summary comes from two DPP combines (pairs, then pairs of pairs; the
     // lower entries win ties, as argmax_max_f64's strict >)
     auto settle_quad = [&](uint32_t t) {
@@ -1200,23 +989,12 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
     // wave-level per-launch counters (scalar registers: ballot popcounts)
     uint32_t c_train = 0, c_eval = 0, c_tep = 0, c_eep = 0;
     unsigned long long *const RSUM = &ACC[4];
-    // RLAMD_RSUM_REG: this lane's finished training episodes' rint(reward * 2^16),
-    // summed in registers (int64 adds are exact and order free)
-    int64_t rsum_lane = 0;
 
-    // FrozenLake family, one action per step (no reset-and-step): the step's table
-    // word trans[(s, a)] is read a step ahead (after the previous selection)
-    // (a registered map's reset lands on a start cell the word was not read for: its
-    // variant reads the word in the step)
-    constexpr bool TRPF = RLAMD_TRPF && RS == 0 &&
-                          (ENV == RL_ENV_FROZEN_LAKE || ENV == RL_ENV_FROZEN_LAKE_EDITED);
-    uint32_t wpf = 0;
-    if constexpr (TRPF) wpf = tabs.trans[tidx<LDS_AM, 4>(tabs, L.s, L.a)];
     // Taxi: the transition word of the lane's (s, a) from the host's table (HBM, 12 KB:
     // L2-resident), read one step ahead — after the selection that fixes the next
     // step's action — instead of decoding / encoding the state (rl_taxi.h taxi_word,
     // which the host checked equal to the table); not with the reset-and-step schedule
-    constexpr bool TXPF = RLAMD_TAXI_PF && ENV == RL_ENV_TAXI && (UCB || RS == 0);
+    constexpr bool TXPF = ENV == RL_ENV_TAXI && (UCB || RS == 0);
     uint32_t wtx = 0;
     if constexpr (TXPF) wtx = p.trans[(L.s < S ? L.s : 0u) * (uint32_t)A + (L.a < (uint32_t)A ? L.a : 0u)];
     // reset-and-step in effect (uniform over the block)
@@ -1239,7 +1017,7 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
         bool fused = false;
         if constexpr (!UCB && RS != 0) {   // RS: the schedule as a compile-time constant (-1: KParams)
             if (RS == 1 || p.reset_step) {
-                if (doR && RLAMD_LAZY_ROWS && !FUSE_MAX) {
+                if (doR && !FUSE_MAX) {      // the row read only by the exploiting lanes
                     const uint32_t s0 = E::reset(L.z, L.rng, tabs);
                     L.ready = true;
                     L.a = select_lazy(s0);
@@ -1248,7 +1026,7 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
                     L.epi_reward = 0.0;
                     L.epi_len = 0;
                     fused = true;
-                } else if (doR) {
+                } else if (doR) {            // FUSE_MAX: the row's argmax in one pass, as the step's
                     const uint32_t s0 = E::reset(L.z, L.rng, tabs);
                     L.ready = true;
                     load_rows(s0, ra2, rb2);
@@ -1259,16 +1037,12 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
 #pragma unroll
                             for (int i = 0; i < A; ++i) v[i] = as_f64(ra2[i]);
                             pre = (int32_t)argmax_max_f64<A>(v, m);
-                        } else if constexpr (QSH) {
-                            if (rmx) {
-                                pre = (int32_t)(uint32_t)f64_bits(RM[s0].y);
-                            } else {
-                                double v[A], m;
-                                qd_row(s0, v);
-                                pre = (int32_t)argmax_max_f64<A>(v, m);
-                            }
+                        } else if (rmx) {    // the fixed point: QSH
+                            pre = (int32_t)(uint32_t)f64_bits(RM[s0].y);
                         } else {
-                            pre = (int32_t)argmax_i64<A>(ra2);
+                            double v[A], m;
+                            qd_row(s0, v);
+                            pre = (int32_t)argmax_max_f64<A>(v, m);
                         }
                     }
                     L.a = select(s0, ra2, rb2, pre);
@@ -1284,13 +1058,10 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
         }
         if constexpr (env_fl_family(ENV)) {
             uint32_t pos = L.s;                    // reset or step in one predicated block
-            const uint32_t w = TRPF ? wpf : tabs.trans[tidx<LDS_AM, 4>(tabs, L.s, L.a)];
+            const uint32_t w = tabs.trans[tidx<LDS_AM, 4>(tabs, L.s, L.a)];
             fl_advance<env_fl_edited(ENV), SLIP, LDS_AM, env_map_start(ENV)>(doR, doS, pos, L.z, w, L.rng, tabs, s2,
                                                                              r, term);
             L.ready = doR ? true : (term ? false : L.ready);
-        } else if constexpr (ENV == RL_ENV_BLACKJACK && RLAMD_BJ_ONE_LOOP) {
-            E::advance(doR, doS, L.z, L.a, L.rng, s2, r, term);
-            L.ready = doR ? true : (doS && term ? false : L.ready);
         } else if (doR) {
             s2 = E::reset(L.z, L.rng, tabs);
             L.ready = true;
@@ -1303,7 +1074,7 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
         // the previous step's settle (Q, flags, counters) before this step's reads:
         // the env step above touches no shared table, so it overlaps the settle
         // (reset-and-step reads Q for its reset lanes' selection: barrier at the end of the step)
-        if (RLAMD_LATE_B3 && k > 0 && !rs_on) __syncthreads();
+        if (k > 0 && !rs_on) __syncthreads();
         // UCB + expected SARSA (SPEC): the visible flags of row s2 decide most of
         // the step without Q values or counters (the regime is mostly
         // non-finite rows).  u_0 NaN sticks as the argmax (utils.rs:1-11); any
@@ -1318,36 +1089,24 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
             tgt_nf = ((((P == 2 && !L.dflag) ? f1 : f0) & row_mask) != 0ull);
         }
         const bool train_lane = doS && L.mode == RL_MODE_TRAIN;
-        if constexpr (RLAMD_EARLY_COUNT) {
-            // the step's counters from masks formed here (L.mode changes only in the
-            // bookkeeping): counted at the end, the flags crossed the step's branches
-            // and barriers and each ballot re-materialised its mask (2 VALU each)
-            c_train += (uint32_t)__popcll(__ballot(train_lane));
-            c_tep += (uint32_t)__popcll(__ballot(train_lane && term));
-            if (EPI > 0 || (EPI < 0 && p.episodic)) {
-                const bool ev_lane = doS && L.mode == RL_MODE_EVAL;
-                c_eval += (uint32_t)__popcll(__ballot(ev_lane));
-                c_eep += (uint32_t)__popcll(__ballot(ev_lane && term));
-            }
-        }
         if (!SPEC || !(sel_nan0 && (tgt_nf || !train_lane))) load_rows(s2, ra2, rb2);   // s2 == 0 on idle lanes
         else {
 #pragma unroll
             for (int i = 0; i < A; ++i) ra2[i] = rb2[i] = 0;
         }
-        // RLAMD_QA_EARLY2: the TD's Q(s, a) word (table vt) read with the target rows,
-        // its latency under the selection (L.s, L.a, L.dflag are final here, also
-        // after a fused reset)
+        // traces (not UCB + expected SARSA): the TD's Q(s, a) word (table vt) read with
+        // the target rows, its latency under the selection (L.s, L.a, L.dflag are final
+        // here, also after a fused reset): cfg 4 0.5377 -> 0.5339 ms; on cfg 5's one-step
+        // double tables it measured 0.3528 -> 0.3549, so not there
         int64_t qa_raw_pre = 0;
-        constexpr bool QAE2 = RLAMD_QA_EARLY2 && TRACES && !QSH && !SPEC;
+        constexpr bool QAE2 = TRACES && !SPEC;
         if constexpr (QAE2) {
             if (BJC && !bj_nonterminal(L.s)) qa_raw_pre = 0;   // never a TD source (terminal rows are not stepped from)
             else qa_raw_pre = (int64_t)Q[qi((P == 2 && !L.dflag) ? 1u : 0u, L.s, L.a)];
         }
         uint32_t rm_pad = 0;                // rmx: the row summary's 4th dword (see below)
         double qa_pre = 0.0;                // rmx: Q(s, a) read early
-        int64_t rmax = 0;                   // FUSE_MAX: utils::max of row s2 (the Q-learning target)
-        double rmaxd = 0.0;
+        double rmaxd = 0.0;                 // FUSE_MAX: utils::max of row s2 (the Q-learning target)
         int32_t rarg = -1;
         if constexpr (FUSE_MAX) {
             if constexpr (FQ) {
@@ -1355,8 +1114,10 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
 #pragma unroll
                 for (int i = 0; i < A; ++i) v[i] = as_f64(ra2[i]);
                 rarg = (int32_t)argmax_max_f64<A>(v, rmaxd);
-                if constexpr (RLAMD_FUSE_MAX == 2) asm volatile("" : "+v"(rarg), "+v"(rmaxd));
-            } else if constexpr (QSH) {
+                // pin both here (empty asm): left alone, the compiler sinks the index into
+                // the exploit branch and the max into the TD branch, redoing the compares
+                asm volatile("" : "+v"(rarg), "+v"(rmaxd));
+            } else {                        // the fixed point: QSH
                 if (rmx) {
                     // no pin: the load's wait can sink to the first use (the exploit
                     // branch, the TD), past the eps test and the exploring draw.  Its
@@ -1367,9 +1128,8 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
                     rarg = (int32_t)(uint32_t)f64_bits(rm.y);
                     rm_pad = (uint32_t)(f64_bits(rm.y) >> 32);
                     // Q(s, a) of the TD, read with the summary (one action per step:
-                    // (s, a) is known since the last step; RLAMD_QA_EARLY)
-                    if (RLAMD_QA_EARLY && !rs_on) qa_pre = QD[qi(0u, L.s, L.a)];
-                    if constexpr (RLAMD_RM_PIN) asm volatile("" : "+v"(rarg), "+v"(rmaxd));
+                    // (s, a) is known since the last step)
+                    if (!rs_on) qa_pre = QD[qi(0u, L.s, L.a)];
                 } else {
                     double v[A];
                     if (BJC && !bj_nonterminal(s2)) {
@@ -1381,19 +1141,13 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
                         qd_row(s2, v);
                     }
                     rarg = (int32_t)argmax_max_f64<A>(v, rmaxd);
-                    if constexpr (RLAMD_FUSE_MAX == 2) asm volatile("" : "+v"(rarg), "+v"(rmaxd));
+                    asm volatile("" : "+v"(rarg), "+v"(rmaxd));
                 }
-            } else {
-                rarg = (int32_t)argmax_max_i64<A>(ra2, rmax);
-                // pin both here (empty asm): left alone, the compiler sinks the index into
-                // the exploit branch and the max into the TD branch, redoing the compares
-                if constexpr (RLAMD_FUSE_MAX == 2) asm volatile("" : "+v"(rarg), "+v"(rmax));
             }
         }
         if (alive) a2 = sel_nan0 ? 0u : select(s2, ra2, rb2, rarg);
         // the next step's table word (s2, a2) read now: the table is constant, and
         // the read's latency then overlaps the update and its barriers
-        if constexpr (TRPF) wpf = tabs.trans[tidx<LDS_AM, 4>(tabs, s2, a2)];
         if constexpr (TXPF) wtx = p.trans[s2 * (uint32_t)A + a2];
         uint32_t d_own = 0xffffffffu;   // SPEC: the step-count entry this lane folds at step end
         if constexpr (SPEC) {
@@ -1438,9 +1192,7 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
         }
         // ---------------- update (one_step_agent.rs:53-86 / elegibility_traces_agent.rs:61-104)
         // Contributions go to SUM/CNT, never to Q, so no barrier is needed before them.
-        // throughput mode (EPI 0): rl_agent_run leaves every live lane in TRAIN mode
-        // (no eval interleave, no target: after_step<0> never changes a mode)
-        const bool train = (EPI == 0 && RLAMD_RUN_TRAIN) ? doS : (doS && L.mode == RL_MODE_TRAIN);
+        const bool train = doS && L.mode == RL_MODE_TRAIN;
         const uint32_t vt = (P == 2 && !L.dflag) ? 1u : 0u;   // get_values: flag ? alpha : beta
         const uint32_t ut = (P == 2 && L.dflag) ? 1u : 0u;    // update:     flag ? beta : alpha
         double td = 0.0;
@@ -1462,7 +1214,7 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
                 } else if constexpr (QSH) {
                     fq = rmaxd;                            // the f64 image's max (exact)
                 } else {
-                    fq = q_val(FUSE_MAX ? rmax : max_i64<A>(rv));   // utils::max on exact images
+                    fq = q_val(max_i64<A>(rv));            // utils::max on exact images
                 }
             } else if constexpr (ALGO == RL_ALGO_SARSA && !SPEC) {
                 fq = val(pick<A>(rv, a2));
@@ -1503,10 +1255,10 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
                 td = __builtin_nan("");                    // r + gamma * NaN - q
             } else {
                 const uint32_t qidx = qi(vt, L.s, L.a);
-                const double qa = QSH ? ((RLAMD_QA_EARLY && rmx && !rs_on) ? qa_pre : QD[qidx])
+                const double qa = QSH ? ((rmx && !rs_on) ? qa_pre : QD[qidx])
                                       : val(QAE2 ? qa_raw_pre : (int64_t)Q[qidx]);
                 td = r + p.gamma * fq - qa;
-                if constexpr (QSH && !RLAMD_RM_PIN) asm volatile("" ::"v"(rm_pad));
+                if constexpr (QSH) asm volatile("" ::"v"(rm_pad));
             }
         }
         if constexpr (!TRACES) {
@@ -1529,14 +1281,13 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
                 // pass 2: the contribution on its entry's grid, and the count — only
                 // where every contribution was finite: an entry with non-finite kinds
                 // moves by their IEEE sum, which needs neither (settle_fq)
-                if (train && (RLAMD_NF_SKIP == 0 || fin)) {
+                if (train && fin) {
                     const uint32_t w = W[idx];
-                    if (fin && (w >> 28) == 0u) {
+                    if ((w >> 28) == 0u) {
                         const int64_t raw = fq_raw(d, fq_grid(((w >> 16) & 0xfffu) - 1u));
                         if (raw) atomicAdd(&SUM[idx], (unsigned long long)raw);
-                        if (RLAMD_NF_SKIP) atomicAdd(&W[idx], 1u);
+                        atomicAdd(&W[idx], 1u);
                     }
-                    if (!RLAMD_NF_SKIP) atomicAdd(&W[idx], 1u);
                 }
                 __syncthreads();   // all contributions in, all Q reads done
                 if (sweep) { if (tid < PSAL) settle_fq(tid); }
@@ -1545,10 +1296,7 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
                 bool owner = false;
                 if (train) owner = contribute(idx, rint_i64_small(p.lr40 * td), 1u);   // q_fix_inrange(lr * td)
                 __syncthreads();   // all contributions in, all Q reads done
-                if (rmx) {
-                    if constexpr (RLAMD_SETTLE_QUAD) { if (tid < PSAL) settle_quad(tid); }
-                    else { if (tid < PSAL / 2u) settle_pair(tid); }
-                }
+                if (rmx) { if (tid < PSAL) settle_quad(tid); }
                 else if (sweep) { if (tid < PSAL) settle(tid); }
                 else if (owner) settle(idx);
             }
@@ -1592,8 +1340,8 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
                 const uint32_t pk = hid | (ut << 16) | (train ? 1u << 20 : 0u) | (train && term ? 1u << 21 : 0u);
                 const uint32_t C = lay.trc_cap;
                 uint32_t wpos = 0;                             // items kept so far (uniform)
-                constexpr uint32_t U = RLAMD_SWEEP_U;
-                if constexpr (RLAMD_POOL_LREC) {
+                constexpr uint32_t U = SWEEP_U;
+                {
                     // the lane's {td, pk} for its items (same wave: LDS operations of a
                     // wave complete in order, so no barrier between the write and the reads)
                     const uint64_t tb = (uint64_t)__double_as_longlong(td);
@@ -1625,15 +1373,9 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
                     }
 #pragma unroll
                     for (uint32_t u = 0; u < U; ++u) {
-                        const uint32_t il = (tg[u] >> 8) & 63u;
-                        if constexpr (RLAMD_POOL_LREC) {
-                            const uint4 r = LR[il];
-                            tdv[u] = __longlong_as_double((long long)(((uint64_t)r.y << 32) | r.x));
-                            pkv[u] = r.z;
-                        } else {
-                            tdv[u] = __shfl(td, (int)il, 64);
-                            pkv[u] = (uint32_t)__shfl((int)pk, (int)il, 64);
-                        }
+                        const uint4 r = LR[(tg[u] >> 8) & 63u];
+                        tdv[u] = __longlong_as_double((long long)(((uint64_t)r.y << 32) | r.x));
+                        pkv[u] = r.z;
                     }
 #pragma unroll
                     for (uint32_t u = 0; u < U; ++u) {
@@ -1642,30 +1384,7 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
                         const bool istr = valid && ((pkv[u] >> 20) & 1u);
                         const bool keep = valid && !((pkv[u] >> 21) & 1u);
                         double en = ev[u];
-                        if constexpr (RLAMD_POOL_BF) {
-                            // branch-free: every valid item adds its contribution and its
-                            // row count — 0 for the items of lanes that do not train this
-                            // step (integer adds of 0 change nothing)
-                            const uint32_t id = tg[u] & 0xffu, uto = P == 2 ? (pkv[u] >> 16) & 1u : 0u;
-                            const double e1 = id == (pkv[u] & 0x1ffu) ? ev[u] + 1.0 : ev[u];
-                            const uint32_t o = id >> 2, b = id & 3u;   // A == 4
-                            const bool first = istr && (tg[u] & 0x8000u);
-                            const double d = p.lr * (tdv[u] * e1);
-                            const bool fin = __builtin_isfinite(d);
-                            // |raw| < 2^51 for finite d (trace_grid_k's guard bits): the magic add
-                            const double y = __builtin_ldexp(d, -e_tr) + 0x1.8p52;
-                            const int64_t raw = (istr && fin)
-                                ? (int64_t)((uint64_t)__double_as_longlong(y) - 0x4338000000000000ull) : (int64_t)0;
-                            if (valid) {
-                                atomicAdd(&SUM[qi(uto, o, b)], (unsigned long long)raw);
-                                atomicAdd(&CNTR[uto * SL + lrow(o)], first ? 1u : 0u);
-                            }
-                            trace_states += first ? 1u : 0u;
-                            if (__builtin_expect(__ballot(istr && !fin) != 0ull, 0)) {   // rare: non-finite kinds
-                                if (istr && !fin) contrib_tr(qi(uto, o, b), d, e_tr);
-                            }
-                            en = istr ? e1 * p.gl : ev[u];
-                        } else if (istr) {
+                        if (istr) {
                             const uint32_t id = tg[u] & 0xffu, uto = P == 2 ? (pkv[u] >> 16) & 1u : 0u;
                             const double e1 = id == (pkv[u] & 0x1ffu) ? ev[u] + 1.0 : ev[u];
                             const uint32_t o = id >> 2, b = id & 3u;   // A == 4
@@ -1678,9 +1397,7 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
                         }
                         const uint64_t m = __ballot(keep);
                         const uint32_t pos = wpos + lanes_below(m);
-                        if (RLAMD_POOL_BF && wpos + 64u <= C) {   // uniform: the round's kept items fit in LDS
-                            if (keep) pool_put(pos, tg[u], en);
-                        } else if (keep) {
+                        if (keep) {
                             if (wpos + 64u <= C || pos < C) pool_put(pos, tg[u], en);
                             else { HT[pos] = (uint16_t)tg[u]; HE[pos] = en; }
                         }
@@ -1704,31 +1421,8 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
                     else { HT[pos] = tag; HE[pos] = en; }
                 }
                 npool = wpos + (uint32_t)__popcll(m);
-            } else if constexpr (PAIRS && RLAMD_COOP_SWEEP) {
-                uint32_t hid = 0xffffu;      // PBITS: the visited pair whose E += 1 the sweep applies
-                if constexpr (PBITS) {
-                    if (train) {
-                        const uint32_t id = L.s * (uint32_t)A + L.a;
-                        const uint32_t w = pbits_word(id >> 5);
-                        if ((w >> (id & 31u)) & 1u) {
-                            hid = id;
-                        } else {
-                            const bool first = ((w >> ((L.s * (uint32_t)A) & 31u)) & 0xfu) == 0u;
-                            const uint16_t tag = (uint16_t)(id | (first ? 0x8000u : 0u));
-                            const uint32_t j = tcnt++;
-                            if (j < pc.cap) {
-                                pc.TRI[pc.ixi(j)] = tag;
-                                pc.TRE[pc.ixe(j)] = 1.0;
-                            } else {
-                                p.tlist[pslot(p, j, lane)] = tag;
-                                p.trace[pslot(p, j, lane)] = 1.0;
-                            }
-                            pbits_set(id);
-                        }
-                    }
-                } else {
-                    if (train) pair_visit<A>(p, pc, lane, L.s, L.a, tcnt);
-                }
+            } else if constexpr (PAIRS) {
+                if (train) pair_visit<A>(p, pc, lane, L.s, L.a, tcnt);
                 // wave-cooperative sweep: the (lane, slot) items of the wave's 64
                 // lanes are dealt out 64 at a time, so a wave takes ceil(sum/64)
                 // rounds instead of its longest list (episode lengths are long-tailed)
@@ -1742,17 +1436,16 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
                 }
                 const uint32_t excl = incl - npl;
                 const uint32_t T = (uint32_t)__shfl((int)incl, 63, 64);
-                // RLAMD_SWEEP_U rounds per iteration, every stage interleaved across
+                // SWEEP_U rounds per iteration, every stage interleaved across
                 // them (owner searches, gathers, loads, then the updates): with 2
                 // waves per SIMD (cfg 4) the rounds' LDS / HBM round trips overlap
                 // instead of queueing one dependent chain per round
-                constexpr uint32_t U = RLAMD_SWEEP_U;
+                constexpr uint32_t U = SWEEP_U;
                 const bool nonempty = npl != 0u;
                 for (uint32_t q0 = 0; q0 < T; q0 += 64u * U) {
                     uint32_t qv[U], lo[U], exo[U];
 #pragma unroll
                     for (uint32_t u = 0; u < U; ++u) { qv[u] = q0 + 64u * u + lid; lo[u] = 0; exo[u] = 0; }
-#if RLAMD_OWNER_SCAN
                     // owner of item q: the last non-empty lane with excl <= q.  The owner of
                     // q0 from one ballot; then the few non-empty lanes whose lists start inside
                     // this iteration's items, in lane order, by readlane (scalar, no LDS
@@ -1777,19 +1470,7 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
                             }
                         }
                     }
-#else
-#pragma unroll
-                    for (uint32_t st = 32; st; st >>= 1) {   // owner: last lane with excl <= q
-#pragma unroll
-                        for (uint32_t u = 0; u < U; ++u) {
-                            const uint32_t e = (uint32_t)__shfl((int)excl, (int)(lo[u] + st), 64);
-                            if (e <= qv[u]) lo[u] += st;
-                        }
-                    }
-#pragma unroll
-                    for (uint32_t u = 0; u < U; ++u) exo[u] = (uint32_t)__shfl((int)excl, (int)lo[u], 64);
-#endif
-                    uint32_t jv[U], utv[U], wv[U], colv[U], hidv[U];
+                    uint32_t jv[U], utv[U], wv[U], colv[U];
                     uint64_t lanev[U];
                     double tdv[U], evv[U];
 #pragma unroll
@@ -1797,7 +1478,6 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
                         jv[u] = qv[u] - exo[u];
                         tdv[u] = __shfl(td, (int)lo[u], 64);
                         utv[u] = P == 2 ? (uint32_t)__shfl((int)ut, (int)lo[u], 64) : 0u;
-                        hidv[u] = PBITS ? (uint32_t)__shfl((int)hid, (int)lo[u], 64) : 0xffffu;
                         lanev[u] = lane - lid + lo[u];        // lanes of a wave are consecutive
                         colv[u] = wbase + lo[u];   // the owner's thread: its slot column
                     }
@@ -1815,7 +1495,7 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
                         if (qv[u] < T) {
                             const uint32_t w = wv[u], j = jv[u], col = colv[u], ut_o = utv[u];
                             const uint32_t id = w & 0x7fffu;
-                            const double ev = (PBITS && id == hidv[u]) ? evv[u] + 1.0 : evv[u], td_o = tdv[u];
+                            const double ev = evv[u], td_o = tdv[u];
                             const bool in_lds = j < pc.cap;
                             const uint32_t o = id / (uint32_t)A, b = id - o * (uint32_t)A;
                             if (w & 0x8000u) {                    // the state's row: n += 1
@@ -1831,18 +1511,6 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
                         }
                     }
                 }
-            } else if constexpr (PAIRS) {
-                if (train) pair_visit<A>(p, pc, lane, L.s, L.a, tcnt);
-                pair_sweep(p, pc, lane, train ? tcnt : 0u, [&](uint32_t id, bool first, double ev) {
-                    const uint32_t o = id / (uint32_t)A, b = id - o * (uint32_t)A;
-                    if (first) {                              // the state's row: n += 1
-                        ++trace_states;
-                        const uint32_t rid = ut * SL + lrow(o);
-                        if (rsweep) atomicAdd(&CNTR[rid], 1u);
-                        else if (atomicAdd(&CNTR[rid], 1u) == 0u) LIST[atomicAdd(&LISTN[0], 1u)] = (uint16_t)rid;
-                    }
-                    contrib_tr(qi(ut, o, b), p.lr * (td * ev), e_tr);
-                });
             } else {
                 if (train) trace_visit<A>(p, lane, L.s, L.a, tcnt);
                 const uint32_t nv = train ? tcnt : 0u;
@@ -1888,23 +1556,20 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
                         if (!(w & 0x8000u)) continue;
                         const uint32_t o = (w & 0x7fffu) / (uint32_t)A;
                         uint32_t taken = 0;
-                        if constexpr (PBITS) {
-                            taken = (pbits_word((o * (uint32_t)A) >> 5) >> ((o * (uint32_t)A) & 31u)) & 0xfu;
-                        } else {
-                            for (uint32_t i = 0; i < tcnt; ++i) {
-                                const uint32_t x = (id_at(i) & 0x7fffu) - o * (uint32_t)A;
-                                if (x < (uint32_t)A) taken |= 1u << x;
-                            }
+                        for (uint32_t i = 0; i < tcnt; ++i) {
+                            const uint32_t x = (id_at(i) & 0x7fffu) - o * (uint32_t)A;
+                            if (x < (uint32_t)A) taken |= 1u << x;
                         }
                         for (uint32_t b = 0; b < (uint32_t)A; ++b)
                             if (!((taken >> b) & 1u)) contrib_tr(qi(ut, o, b), dn, e_tr);
                     }
                 }
                 if (train && term) {
-                    if constexpr (!POOL) pair_clear(p, pc, lane, tcnt);
-                    if constexpr (PBITS) {
+                    if constexpr (POOL) {
 #pragma unroll
                         for (int i = 0; i < PBW; ++i) pbits[i] = 0u;
+                    } else {
+                        pair_clear(p, pc, lane, tcnt);
                     }
                 }
             }
@@ -1935,35 +1600,9 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
         // Q_{t+1} complete before the next step's reads (one action per step: after
         // the next step's env step instead, below; reset-and-step reads Q first —
         // and a barrier between its deal and its reads measured 0.98x on cfg 5)
-        if (!RLAMD_LATE_B3 || rs_on) __syncthreads();
+        if (rs_on) __syncthreads();
         bool tr = false, ev = false;
-        if constexpr (!INSTR && RLAMD_TAIL) {
-            // one predicated block (no STEP / RESET branches): the STEP lanes'
-            // bookkeeping computed for every lane, then every lane-state field written
-            // once by a select — RESET lanes start an episode, idle lanes keep theirs
-            if (train) {
-                if (P == 2) L.dflag = !L.dflag;            // after_update
-                if constexpr (!UCB) {                      // decay_epsilon: one select per lane
-                    const double nw = L.eps * p.eps_dm - p.eps_ds;
-                    L.eps = (term && !(p.eps_final > nw)) ? nw : L.eps;
-                }
-            }
-            LaneRegs N = L;
-            after_step<EPI>(p, N, s2, a2, r, term, tr, ev);   // term is false on RESET / idle lanes
-            const bool act = doS || doR;
-            L.epi_reward = doS ? N.epi_reward : (doR ? 0.0 : L.epi_reward);
-            L.epi_len = doS ? N.epi_len : (doR ? 0u : L.epi_len);
-            L.s = act ? s2 : L.s;
-            L.a = act ? a2 : L.a;
-            L.train_ep = doS ? N.train_ep : L.train_ep;
-            L.mode = doS ? N.mode : L.mode;
-            L.eval_left = doS ? N.eval_left : L.eval_left;
-            L.need_reset = doS ? N.need_reset : (doR ? false : L.need_reset);
-            tr = tr && doS;
-            ev = ev && doS;
-            if (tr) atomicAdd(RSUM, (unsigned long long)(FQ ? (int64_t)__builtin_rint(L.epi_reward * 65536.0)
-                                                             : rint_i64_small(L.epi_reward * 65536.0)));
-        } else if (doS) {
+        if (doS) {
             if (train) {
                 if (P == 2) L.dflag = !L.dflag;            // after_update
                 if constexpr (!UCB) {                      // decay_epsilon: one select per lane
@@ -1975,13 +1614,8 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
             after_step<EPI>(p, L, s2, a2, r, term, tr, ev);
             // fixed point: the host also proved |episode reward| * 2^16 < 2^51
             // (delta_bound), so rint is the magic add
-            if constexpr (RLAMD_RSUM_REG && !INSTR) {
-                const int64_t rq = FQ ? (int64_t)__builtin_rint(L.epi_reward * 65536.0) : rint_i64_small(L.epi_reward * 65536.0);
-                rsum_lane += tr ? rq : (int64_t)0;
-            } else {
-                if (tr) atomicAdd(RSUM, (unsigned long long)(FQ ? (int64_t)__builtin_rint(L.epi_reward * 65536.0)
-                                                                 : rint_i64_small(L.epi_reward * 65536.0)));
-            }
+            if (tr) atomicAdd(RSUM, (unsigned long long)(FQ ? (int64_t)__builtin_rint(L.epi_reward * 65536.0)
+                                                             : rint_i64_small(L.epi_reward * 65536.0)));
             if (INSTR && p.elog && (tr || ev)) log_episode(p, lane, L, tr);
         } else if (doR) {
             L.s = s2;
@@ -1993,13 +1627,11 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
         } else if (INSTR && p.rec && active) {
             write_record(p, k, lane, 0u, 0u, 0u, 0u, 0u, 0.0, false, 0.0, RL_MODE_DONE);
         }
-        if constexpr (!RLAMD_EARLY_COUNT) {
-            c_train += (uint32_t)__popcll(__ballot(train));
-            c_tep += (uint32_t)__popcll(__ballot(tr));
-            if (EPI > 0 || (EPI < 0 && p.episodic)) {   // run(): lanes only train, so no eval steps / episodes
-                c_eval += (uint32_t)__popcll(__ballot(doS && !train));
-                c_eep += (uint32_t)__popcll(__ballot(ev));
-            }
+        c_train += (uint32_t)__popcll(__ballot(train));
+        c_tep += (uint32_t)__popcll(__ballot(tr));
+        if (EPI > 0 || (EPI < 0 && p.episodic)) {   // run(): lanes only train, so no eval steps / episodes
+            c_eval += (uint32_t)__popcll(__ballot(doS && !train));
+            c_eep += (uint32_t)__popcll(__ballot(ev));
         }
     }
 
@@ -2019,10 +1651,6 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
         if constexpr (PAIRS) { if (active) pair_cache_store(p, pc, lane, tcnt); }
     }
     {
-        if constexpr (RLAMD_RSUM_REG && !INSTR) {
-            const int64_t rw = wave_sum_i64(rsum_lane);
-            if ((tid & 63u) == 0 && rw) atomicAdd(RSUM, (unsigned long long)rw);
-        }
         const uint32_t c_done = (uint32_t)__popcll(__ballot(active && L.mode == RL_MODE_DONE));
         if ((tid & 63u) == 0) {
             if (c_train) atomicAdd(&ACC[0], (unsigned long long)c_train);
@@ -2076,32 +1704,15 @@ __global__ void __launch_bounds__(1024) k_train_shared(KParams p) {
 }
 // the throughput mode (rl_agent_run) with the episodic bookkeeping compiled out,
 // as k_train_shared_o8<..., EPI = 0>
-#ifndef RLAMD_SHARED_RUNMODE
-#define RLAMD_SHARED_RUNMODE 1
-#endif
 template <int ENV, int AGENT, int POLICY, int SEL, int ALGO, bool FQ>
 __global__ void __launch_bounds__(1024) k_train_shared_run(KParams p) {
     train_shared_body<ENV, AGENT, POLICY, SEL, ALGO, false, FQ, -1, -1, false, -1, 0>(p);
-}
-// Eligibility traces on the small tables (FrozenLake, CliffWalking: the pair
-// bitmap) in groups of <= 256 lanes, at most 2 groups per CU (cfg 4: 2^17 lanes in
-// 512 groups): 2 waves per SIMD is all the lanes give, so a wave may hold 256
-// VGPRs — the sweep's interleaved rounds and the bitmap stay in registers instead
-// of the 128-VGPR bound's scratch spills
-template <int ENV, int AGENT, int POLICY, int SEL, int ALGO>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) k_train_shared_w(KParams p) {
-    train_shared_body<ENV, AGENT, POLICY, SEL, ALGO, false, true>(p);
-}
-template <int ENV, int AGENT, int POLICY>
-constexpr bool use_w() {
-    return RLAMD_TRACES_W && AGENT == RL_AGENT_TRACES && POLICY != RL_POLICY_NEURAL &&
-           (ENV == RL_ENV_CLIFF_WALKING || env_fl_family(ENV));
 }
 // the shared kernel for the agent's representation (nullptr: the fixed point
 // cannot be proven for this variant, so the host never asks for it)
 template <int ENV, int AGENT, int POLICY, int SEL, int ALGO, bool INSTR>
 const void *shared_kernel(const KParams &p) {
-    const bool run = RLAMD_SHARED_RUNMODE && !INSTR && !p.episodic;
+    const bool run = !INSTR && !p.episodic;
     if (p.fq) return run ? (const void *)k_train_shared_run<ENV, AGENT, POLICY, SEL, ALGO, true>
                          : (const void *)k_train_shared<ENV, AGENT, POLICY, SEL, ALGO, INSTR, true>;
     if constexpr (fix_possible<AGENT, POLICY, SEL, ALGO>())
@@ -2115,22 +1726,17 @@ const void *shared_kernel(const KParams &p) {
 // eps-greedy Blackjack (single or double table) in the fixed point or in f64.
 // The other variants would spill for no occupancy.
 // MODE 1: fixed point; 2: fixed point with packed (sum, count) contributions; 3: f64
-#ifndef RLAMD_O8_WAVES
-#define RLAMD_O8_WAVES 8   // waves per SIMD the o8 kernels are compiled for
-#endif
+constexpr int O8_WAVES = 8;   // waves per SIMD the o8 kernels are compiled for
 // EPI 0: the throughput mode (rl_agent_run, no episode target or eval interleave)
 // with the episodic bookkeeping compiled out (fewer live scalars in the step loop);
 // -1: either, by KParams::episodic (train / evaluate)
-#ifndef RLAMD_O8_RUNMODE
-#define RLAMD_O8_RUNMODE 1
-#endif
 template <int ENV, int AGENT, int POLICY, int SEL, int ALGO, int SLIP, int SWEEP, int MODE, int RS, int EPI>
-__global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(RLAMD_O8_WAVES, RLAMD_O8_WAVES))) k_train_shared_o8(KParams p) {
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(O8_WAVES, O8_WAVES))) k_train_shared_o8(KParams p) {
     train_shared_body<ENV, AGENT, POLICY, SEL, ALGO, false, MODE == 3, SLIP, SWEEP, MODE == 2, RS, EPI>(p);
 }
 template <int ENV, int AGENT, int POLICY, int SEL, int ALGO, int SLIP, int SWEEP, int MODE, int RS>
 const void *o8_epi(const KParams &p) {
-    if (RLAMD_O8_RUNMODE && !p.episodic)
+    if (!p.episodic)
         return (const void *)k_train_shared_o8<ENV, AGENT, POLICY, SEL, ALGO, SLIP, SWEEP, MODE, RS, 0>;
     return (const void *)k_train_shared_o8<ENV, AGENT, POLICY, SEL, ALGO, SLIP, SWEEP, MODE, RS, -1>;
 }
@@ -2222,12 +1828,6 @@ __global__ void __launch_bounds__(256) k_train_private(KParams p) {
 // parameters three times per step and writes them once (6.3 KB per env-step,
 // 421 GB per cfg 6 launch at 0.52 of HBM peak); here the step loop touches no
 // parameter memory.  Same operations in the same order: bit-identical.
-#ifndef RLAMD_NET_PAIR
-#define RLAMD_NET_PAIR 1   // NeuralPolicy: the step's two predicts in one parameter pass
-#endif
-#ifndef RLAMD_NET_REGS
-#define RLAMD_NET_REGS 1
-#endif
 template <int ENV, int AGENT, int SEL, int ALGO>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) k_train_private_net(KParams p) {
     using E = EnvDev<ENV>;
@@ -2265,7 +1865,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 // (and launch_train) also require the bin's shape and activations at run time
 template <int ENV, int AGENT, int POLICY>
 __host__ __device__ constexpr bool use_net_regs() {
-    return RLAMD_NET_REGS && POLICY == RL_POLICY_NEURAL && AGENT == RL_AGENT_ONE_STEP && env_fl_plain(ENV);
+    return POLICY == RL_POLICY_NEURAL && AGENT == RL_AGENT_ONE_STEP && env_fl_plain(ENV);
 }
 
 // Private agents with small tables (KParams::priv_lpw != 0; FrozenLake 4x4 / 8x8,
@@ -2390,7 +1990,7 @@ struct PrivAgent {
     // Policy::predict (tabular_policy.rs:27-29, double_tabular_policy.rs:31-40, neural_policy.rs:43-47)
     __device__ __forceinline__ void predict(uint32_t s, double (&v)[A]) {
         if constexpr (NEURAL) {
-            if constexpr (RLAMD_NET_PAIR) nc.take(nc_b, s);
+            nc.take(nc_b, s);
             nc.get(p, net, s);
 #pragma unroll
             for (int i = 0; i < A; ++i) v[i] = nc.y[i];
@@ -2415,7 +2015,7 @@ struct PrivAgent {
     // Policy::update with x = td (one-step) or td * E[o][b] (traces)
     __device__ __forceinline__ void pol_update(uint32_t tbl, uint32_t s, uint32_t a, double x) {
         if constexpr (NEURAL) {
-            if constexpr (RLAMD_NET_PAIR) nc.take(nc_b, s);
+            nc.take(nc_b, s);
             net_policy_update<A>(p, net, nc, s, a, x);
             nc_b.invalidate();                                  // the parameters changed
         } else {
@@ -2427,7 +2027,7 @@ struct PrivAgent {
     // update's get_values(s) — in one pass over the parameters (the same values:
     // nothing changes the parameters between them)
     __device__ __forceinline__ void prefetch_pair(uint32_t s2, uint32_t s) {
-        if constexpr (NEURAL && RLAMD_NET_PAIR) nc.get_pair(p, net, s2, nc_b, s);
+        if constexpr (NEURAL) nc.get_pair(p, net, s2, nc_b, s);
     }
     // Agent::get_action (one_step_agent.rs:48-51) with the reference's immediate UCB increments
     __device__ __forceinline__ uint32_t select(uint32_t s) {
@@ -2519,21 +2119,21 @@ struct PrivAgent {
                 mslot[key] = mc + 1u;
                 ++mc;
             }
-            if constexpr (!UCB && !NEURAL && RLAMD_PLAN_PF) {
+            if constexpr (!UCB && !NEURAL) {
                 // eps-greedy draws depend on the stream and eps only, never on Q: a batch
                 // of planning steps takes its draws first (gen_index, the eps test, the
                 // exploring action: the order of the loop below), issues its model reads
                 // together, then runs the selections and updates in order — the exploit
                 // argmax reads Q after the previous planning updates, as the loop does
-                // RLAMD_PLAN_PB steps per batch (cfg 7, 10 planning steps: 4 -> 20.28 ms per
+                // PLAN_PB steps per batch (cfg 7, 10 planning steps: 4 -> 20.28 ms per
                 // launch, 8 -> 19.70, 16 -> 18.99, profiles/r05/cfg7_plan_batch.txt)
-                constexpr uint32_t PB = RLAMD_PLAN_PB;
-                for (uint32_t i0 = 0; i0 < p.plan_steps; i0 += PB) {
-                    const uint32_t nb = p.plan_steps - i0 < PB ? p.plan_steps - i0 : PB;
-                    uint4 m[PB];
-                    std::conditional_t<(PB > 8), uint64_t, uint32_t> acts = 0;                        // 4 bits per step: action + 1, 0 = exploit
+                constexpr uint32_t PLAN_PB = 16;
+                for (uint32_t i0 = 0; i0 < p.plan_steps; i0 += PLAN_PB) {
+                    const uint32_t nb = p.plan_steps - i0 < PLAN_PB ? p.plan_steps - i0 : PLAN_PB;
+                    uint4 m[PLAN_PB];
+                    uint64_t acts = 0;   // 4 bits per step: action + 1, 0 = exploit
 #pragma unroll
-                    for (uint32_t b = 0; b < PB; ++b) {
+                    for (uint32_t b = 0; b < PLAN_PB; ++b) {
                         if (b < nb) {
                             const uint32_t j = gen_index(L.rng, mc);
                             uint32_t a1 = 0;
@@ -2543,7 +2143,7 @@ struct PrivAgent {
                         }
                     }
 #pragma unroll
-                    for (uint32_t b = 0; b < PB; ++b) {
+                    for (uint32_t b = 0; b < PLAN_PB; ++b) {
                         if (b < nb) {
                             const uint32_t pk = m[b].x, ps2 = m[b].y;
                             const double pr = __longlong_as_double((long long)(((uint64_t)m[b].w << 32) | m[b].z));
@@ -2690,9 +2290,6 @@ hipError_t launch_train(const KParams &p, dim3 grid, dim3 block, size_t smem, hi
                 k = sw ? o8_kernel<ENV, AGENT, POLICY, SEL, ALGO, -1, 1>(p)
                        : o8_kernel<ENV, AGENT, POLICY, SEL, ALGO, -1, -1>(p);
             }
-        } else if constexpr (use_w<ENV, AGENT, POLICY>()) {
-            // 256 CUs: <= 512 groups keeps the grid at <= 2 groups (2 waves per SIMD) per CU
-            if (p.fq && block.x <= 256 && grid.x <= 512) k = (const void *)k_train_shared_w<ENV, AGENT, POLICY, SEL, ALGO>;
         }
         if (!k) k = shared_kernel<ENV, AGENT, POLICY, SEL, ALGO, false>(p);
     }

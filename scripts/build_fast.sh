@@ -4,7 +4,9 @@
 # plus rl_misc / rl_host from the current sources (the LDS carve and the host agree);
 # the other env TUs are compiled empty (no kernels: a small .so to ship).  Timing and
 # targeted parity only.
-#   NAME=rowmax TU=frozen_lake ONLY=0,0,0,1,0 EXTRA="-DRLAMD_ROWMAX=0" scripts/build_fast.sh
+#   NAME=cfg2 TU=frozen_lake ONLY=0,0,0,1,0 scripts/build_fast.sh
+# EXTRA: further compiler flags (e.g. the -D switch a scripts/*.patch adds, with
+# SRCDIR a patched copy of the sources)
 set -e
 cd "$(dirname "$0")/../rl-rust_amd"
 mkdir -p exp

@@ -6,7 +6,7 @@
 // selection, recorded from the real agent by scripts/cfg4_sweep_floor.py: one u16
 // per (launch, step, lane) = pair id s*4+a (bits 0-7) | trains (8) | episode ends
 // (9).  Per step, exactly as k_train_shared's pool path (rl_train_impl.h, POOL with
-// RLAMD_POOL_LREC, U = RLAMD_SWEEP_U = 4; elegibility_traces_agent.rs:75-101):
+// the lane records LR, U = SWEEP_U = 4; elegibility_traces_agent.rs:75-101):
 //   - the lane's visited-pair bits decide hit (E += 1 inside the sweep) or new pair
 //     (contributes after the sweep, joins the pool unless its episode ends);
 //   - the lane writes its 16-byte {td, pk} record; the wave sweeps its pool 64
