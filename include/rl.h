@@ -111,7 +111,7 @@ enum rl_q_mode {        /* rl_agent_set_q_mode */
 typedef struct rl_env_config {
     int32_t kind;       /* rl_env_kind */
     int32_t map8x8;     /* FrozenLake: 0 = MAP_4X4, 1 = MAP_8X8 (frozen_lake.rs:23-28), or an id
-                           from rl_map_register (>= 2): the caller's own map */
+                           from rl_map_register / rl_map_register_wide (>= 2): the caller's own map */
     int32_t slippery;   /* FrozenLake --stochastic_env */
     uint32_t max_steps; /* truncation (frozen_lake.rs:119); ignored by Blackjack */
 } rl_env_config;
@@ -233,15 +233,33 @@ int rl_obs_from_reference(int32_t env_kind, uint64_t obs, uint32_t *dense_state)
  * Draws: reset draws one uniform01 only when the map has two or more 'S' cells; one
  * 'S' anywhere is a fixed start and no 'S' starts every episode at cell 0 (the
  * reference's all-false argmax, utils.rs:33-43), neither drawn.
- * Limit: at most RL_MAP_MAX_CELLS cells — the packed transition table holds a
- * 6-bit next state and the traces pair pool tags (state, action) pairs with 8 bits
- * (S * A <= 256).  Larger maps would need a second table format and are rejected.
+ * Limits: rl_map_register takes at most RL_MAP_MAX_CELLS cells — the packed
+ * transition table holds a 6-bit next state and the traces pair pool tags (state,
+ * action) pairs with 8 bits (S * A <= 256).  rl_map_register_wide takes up to
+ * RL_MAP_WIDE_MAX_CELLS cells in a second table format: the three slippery outcomes
+ * of (s, a) are the deterministic outcomes of directions (a-1)%4, a, (a+1)%4
+ * (frozen_lake.rs:32-46), so the wide table keeps one 16-bit word per (state,
+ * direction) with a 10-bit next state, and shared-mode traces keep per-lane pair
+ * lists instead of the pool.  Both formats compute the same env: a wide copy of a
+ * map gives the same streams, tables and agents bit for bit.
+ * Every agent / policy / selector / algo combination is guaranteed on maps of at
+ * most 256 cells.  Above 256 cells a shared-mode combination either runs or fails
+ * with RL_E_ARG at rl_agent_create, when its learner group's tables do not fit the
+ * 160 KiB LDS (the message gives the bytes needed): e.g. the double policy in f64
+ * at 1024 cells.
  * RL_E_ARG (with a message) for: zero rows or columns, ragged rows, a letter outside
- * SFHG, more than RL_MAP_MAX_CELLS cells, an unknown id; all before any HIP call. */
+ * SFHG, more cells than the function's limit, an unknown id; all before any HIP call. */
 #define RL_MAP_MAX_CELLS 64
+#define RL_MAP_WIDE_MAX_CELLS 1024
 /* FrozenLakeEnv::new / FrozenLakeEditedEnv::new with the caller's map: rows of equal
  * length over {S,F,H,G}.  *map_id >= 2; the same rows give the same id again. */
 int rl_map_register(const char *const *rows, uint32_t n_rows, int32_t *map_id);
+/* The same with the wide table format, for 1..RL_MAP_WIDE_MAX_CELLS cells.  Always a
+ * wide-format map, whatever its size: the same rows registered through the two
+ * functions get two ids; registered here again they get the same id. */
+int rl_map_register_wide(const char *const *rows, uint32_t n_rows, int32_t *map_id);
+/* *wide = 1 for an id from rl_map_register_wide, 0 for ids 0 / 1 and rl_map_register's */
+int rl_map_is_wide(int32_t map_id, int32_t *wide);
 /* rows x cols and the cells (row-major, no terminators) of a map id; 0 / 1 are the
  * built-ins.  cells may be NULL (dimensions only); else n must be rows * cols. */
 int rl_map_info(int32_t map_id, uint32_t *n_rows, uint32_t *n_cols, char *cells, size_t n);

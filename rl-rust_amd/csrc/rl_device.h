@@ -762,6 +762,82 @@ template <int BASE> struct EnvDevMap {
 template <> struct EnvDev<ENV_FL_MAP> : EnvDevMap<RL_ENV_FROZEN_LAKE> {};
 template <> struct EnvDev<ENV_FLE_MAP> : EnvDevMap<RL_ENV_FROZEN_LAKE_EDITED> {};
 
+// Wide maps (rl_map_register_wide, up to RL_MAP_WIDE_MAX_CELLS = 1024 cells).  The
+// three slippery outcomes of (s, a) are the deterministic outcomes of directions
+// (a-1)%4, a, (a+1)%4 (frozen_lake.rs:32-46), so the table holds one u16 per
+// (s, direction) — bits 0-9 next state, bit 10 the reward bit (1.0, or 10.0
+// edited; else 0.0 / -1.0), bit 11 terminated (rl_kparams.h WIDE_*) — and a
+// slippery step draws first, then reads direction (a + 3 + i) & 3.  'G' and 'H'
+// cells hold (s, 0, terminated) in all four directions: any i gives the
+// reference's single outcome, so no "slippery row" bit is kept (the draw is
+// still made, as for the packed table).  8 bytes per state instead of the 32 a
+// widened three-outcome word would take.
+template <bool AM>
+__device__ __forceinline__ uint32_t wide_entry(const EnvTables &t, uint32_t s, uint32_t d) {
+    return ((const uint16_t *)t.trans)[tidx<AM, 4>(t, s, d)];
+}
+// outcome index of a slippery step (frozen_lake.rs:126): the categorical draw over [1/3, 1/3, 1/3]
+__device__ __forceinline__ uint32_t slip_index(const EnvTables &t, double u) {
+    return (t.th1 > u) ? 0u : (t.th2 > u) ? 1u : (t.th3 > u) ? 2u : 0u;
+}
+// fl_advance (MAPS) over the wide table: reset-or-step in one predicated block with
+// one draw site; the table entry is read behind the draw.  Every lane reads an
+// entry (pos is a valid state, the direction is masked to 0-3).
+template <bool EDITED, int SLIP, bool AM>
+__device__ __forceinline__ void fl_advance_wide(bool doR, bool doS, uint32_t &pos, uint32_t &z, uint32_t a, Rng &r,
+                                                const EnvTables &t, uint32_t &s2, double &rew, bool &term) {
+    const bool trunc = doS && z >= t.max_steps;
+    const bool st = doS && !trunc;
+    const bool slip = SLIP == 1 || (SLIP < 0 && t.slippery);
+    const bool drawn = t.fixed_start < 0;              // uniform over the launch
+    uint32_t d = a, s0 = drawn ? 0u : (uint32_t)t.fixed_start;
+    if ((slip && st) || (drawn && doR)) {
+        const double u = uniform01(r);
+        d = (slip && st) ? a + 3u + slip_index(t, u) : a;
+        if (drawn) {
+            const uint32_t c = start_list_search(t, u);
+            s0 = doR ? c : 0u;
+        }
+    }
+    const uint32_t o = wide_entry<AM>(t, pos, d & 3u);
+    const double r_bit = EDITED ? 10.0 : 1.0, r_else = EDITED ? -1.0 : 0.0;
+    s2 = st ? (o & WIDE_NEXT_MASK) : ((EDITED && trunc) ? pos : (doR ? s0 : 0u));
+    rew = st ? ((o & WIDE_REWARD) ? r_bit : r_else) : ((EDITED && trunc) ? -1.0 : 0.0);
+    term = trunc || (st && (o & WIDE_TERM) != 0u);
+    z = doR ? 0u : (st ? z + 1u : z);
+    pos = s2;
+}
+// FrozenLakeEnv / FrozenLakeEditedEnv on a wide map: EnvDevMap's reset, and the
+// built-in envs' step (truncation :119-122 / frozen_lake_edited.rs:227-231, one
+// draw per slippery step) over the wide table.  SLIP is read at run time.
+template <bool EDITED> struct EnvDevWide {
+    static constexpr int A = 4;
+    __device__ static __forceinline__ uint32_t reset(uint32_t &z, Rng &r, const EnvTables &t) {
+        z = 0;
+        if (t.fixed_start >= 0) return (uint32_t)t.fixed_start;
+        return start_list_search(t, uniform01(r));
+    }
+    template <int SLIP = -1, bool AM = false>
+    __device__ static __forceinline__ void step(uint32_t &pos, uint32_t &z, uint32_t a, Rng &r,
+                                                const EnvTables &t, uint32_t &s2, double &rew,
+                                                bool &term) {
+        if (z >= t.max_steps) {
+            s2 = EDITED ? pos : 0u; rew = EDITED ? -1.0 : 0.0; term = true;
+            return;
+        }
+        z += 1;
+        uint32_t d = a;
+        if (SLIP == 1 || (SLIP < 0 && t.slippery)) d = a + 3u + slip_index(t, uniform01(r));
+        const uint32_t o = wide_entry<AM>(t, pos, d & 3u);
+        s2 = o & WIDE_NEXT_MASK;
+        rew = (o & WIDE_REWARD) ? (EDITED ? 10.0 : 1.0) : (EDITED ? -1.0 : 0.0);
+        term = (o & WIDE_TERM) != 0;
+        pos = s2;
+    }
+};
+template <> struct EnvDev<ENV_FL_WIDE> : EnvDevWide<false> {};
+template <> struct EnvDev<ENV_FLE_WIDE> : EnvDevWide<true> {};
+
 // CliffWalkingEnv (src/env/cliff_walking.rs): deterministic, no RNG.
 // trans[s*4+a]: bits 0-5 next, bit 6 reward -100 (else -1), bit 7 terminated.
 template <> struct EnvDev<RL_ENV_CLIFF_WALKING> {

@@ -153,11 +153,17 @@ std::vector<Grid> &map_registry() {
     static std::vector<Grid> maps = {Grid(kFL4, kFL4 + 4), Grid(kFL8, kFL8 + 8)};
     return maps;
 }
-bool map_lookup(int32_t id, Grid &out) {
+// the table format of every id (rl_map_register_wide: 1), parallel to the registry
+std::vector<uint8_t> &map_wide_flags() {
+    static std::vector<uint8_t> wide = {0, 0};
+    return wide;
+}
+bool map_lookup(int32_t id, Grid &out, bool *wide = nullptr) {
     std::lock_guard<std::mutex> lock(g_map_mu);
     const std::vector<Grid> &maps = map_registry();
     if (id < 0 || (size_t)id >= maps.size()) return false;
     out = maps[(size_t)id];
+    if (wide) *wide = map_wide_flags()[(size_t)id] != 0;
     return true;
 }
 
@@ -168,7 +174,8 @@ int build_env(const rl_env_config &c, EnvHost &e) {
     e.max_steps = c.max_steps;
     if (c.kind == RL_ENV_FROZEN_LAKE || c.kind == RL_ENV_FROZEN_LAKE_EDITED) {
         const bool edited = c.kind == RL_ENV_FROZEN_LAKE_EDITED;
-        if (!map_lookup(c.map8x8, e.map))
+        bool wide = false;
+        if (!map_lookup(c.map8x8, e.map, &wide))
             return fail(RL_E_ARG, "unknown FrozenLake map id " + std::to_string(c.map8x8) +
                                       " (0 = MAP_4X4, 1 = MAP_8X8, else an id from rl_map_register)");
         const Grid &map = e.map;
@@ -179,6 +186,7 @@ int build_env(const rl_env_config &c, EnvHost &e) {
         // a registered map runs the kernels with the start variant (rl_kparams.h), a
         // built-in one exactly the instantiations it always ran
         if (c.map8x8 >= 2) e.kenv = edited ? ENV_FLE_MAP : ENV_FL_MAP;
+        if (wide) e.kenv = edited ? ENV_FLE_WIDE : ENV_FL_WIDE;   // rl_map_register_wide: the wide table
         e.S = (uint32_t)(nrow * ncol);
         e.A = 4;
         e.trans.assign(e.S * 4, 0);
@@ -187,18 +195,29 @@ int build_env(const rl_env_config &c, EnvHost &e) {
         e.start.assign(e.S, 0.0);   // frozen_lake.rs:52-65: 1/k on each of the k 'S' cells
         for (int i = 0; i < nrow * ncol; ++i)
             if (map[i / ncol][i % ncol] == 'S') e.start[i] = 1.0 / n_start;
-        auto outcome = [&](int row, int col, int a) -> uint32_t {
+        // the deterministic outcome of direction a: next state, reward bit, terminated
+        auto judge = [&](int row, int col, int a, uint32_t &ns, bool &goal, bool &done) {
             int nr, nc;
             grid_move(nrow, ncol, row, col, a, nr, nc);
+            ns = (uint32_t)(nr * ncol + nc);
             if (edited) {   // update_probability_matrix (frozen_lake_edited.rs:94-113): judged by
                             // the terrain in the moved direction; 10.0 onto G, else -1.0
                 const int t = neighbour(map, nrow, ncol, row, col, a);
-                return (uint32_t)(nr * ncol + nc) | (t == kGoal ? 64u : 0u) | ((t == kGoal || t == kHole) ? 128u : 0u);
+                goal = t == kGoal;
+                done = t == kGoal || t == kHole;
+            } else {
+                const char ch = map[nr][nc];
+                goal = ch == 'G';
+                done = ch == 'G' || ch == 'H';
             }
-            const char ch = map[nr][nc];
-            return (uint32_t)(nr * ncol + nc) | (ch == 'G' ? 64u : 0u) | ((ch == 'G' || ch == 'H') ? 128u : 0u);
         };
-        for (int row = 0; row < nrow; ++row)
+        auto outcome = [&](int row, int col, int a) -> uint32_t {   // the packed byte (<= 64 cells)
+            uint32_t ns;
+            bool goal, done;
+            judge(row, col, a, ns, goal, done);
+            return ns | (goal ? 64u : 0u) | (done ? 128u : 0u);
+        };
+        for (int row = 0; !wide && row < nrow; ++row)
             for (int col = 0; col < ncol; ++col)
                 for (int a = 0; a < 4; ++a) {
                     const int s = row * ncol + col;
@@ -211,6 +230,26 @@ int build_env(const rl_env_config &c, EnvHost &e) {
                     else w = outcome(row, col, a);
                     e.trans[s * 4 + a] = w;
                 }
+        if (wide) {
+            // the wide table (rl_kparams.h): one u16 per (s, direction), two per u32
+            // word; 'G' / 'H' cells (s, 0, terminated) in every direction
+            std::vector<uint16_t> t16((size_t)e.S * 4);
+            for (int row = 0; row < nrow; ++row)
+                for (int col = 0; col < ncol; ++col)
+                    for (int d = 0; d < 4; ++d) {
+                        const int s = row * ncol + col;
+                        const char ch = map[row][col];
+                        uint32_t ns;
+                        bool goal, done;
+                        judge(row, col, d, ns, goal, done);
+                        t16[(size_t)s * 4 + d] =
+                            (ch == 'G' || ch == 'H')
+                                ? (uint16_t)((uint32_t)s | WIDE_TERM)
+                                : (uint16_t)(ns | (goal ? WIDE_REWARD : 0u) | (done ? WIDE_TERM : 0u));
+                    }
+            e.trans.assign((size_t)e.S * 2, 0);
+            std::memcpy(e.trans.data(), t16.data(), t16.size() * 2);
+        }
         e.slippery = c.slippery ? 1 : 0;
         const double third = 1.0 / 3.0;
         e.th1 = 0.0 + third;
@@ -569,6 +608,12 @@ void peer_free(rl_agent *a);
 int peer_check(rl_agent *a);
 int peer_selftest(rl_agent *a, bool *ok);
 
+// the LDS guard: a learner group's carve (rl_train_impl.h smem_layout) past the CU's LDS
+int lds_guard_fail(size_t need) {
+    return fail(RL_E_ARG, "learner-group tables exceed the 160 KiB LDS (" + std::to_string(need) +
+                              " bytes needed, " + std::to_string(160 * 1024) + " available)");
+}
+
 int agent_select_kernel(rl_agent *a) {
     a->fn = lookup_train(a->eh.kenv, a->cfg.agent, a->cfg.policy, a->cfg.selector, a->cfg.algo,
                          a->priv ? 1 : 0);
@@ -640,7 +685,8 @@ int agent_select_kernel(rl_agent *a) {
             const bool pool = a->cfg.agent == RL_AGENT_TRACES && a->cfg.policy != RL_POLICY_NEURAL &&
                               !(a->cfg.selector == RL_SEL_UCB && a->cfg.algo == RL_ALGO_EXPECTED_SARSA) &&
                               (ek == RL_ENV_CLIFF_WALKING || ek == RL_ENV_FROZEN_LAKE ||
-                               ek == RL_ENV_FROZEN_LAKE_EDITED);
+                               ek == RL_ENV_FROZEN_LAKE_EDITED) &&
+                              !env_wide(a->eh.kenv);   // wide maps run the pair lists, not the pool
             int ncu = 256;
             (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, a->device);
             if (pool && ((uint64_t)a->L + 63u) / 64u < 16ull * (uint64_t)ncu) lpw = 32;
@@ -667,6 +713,9 @@ int agent_select_kernel(rl_agent *a) {
             const size_t base = shared_smem_bytes(a->eh.kenv, a->cfg.agent, a->cfg.policy, a->cfg.selector,
                                                   a->cfg.algo, a->S, a->A, a->eh.dev_n_start(), a->block.x, 0,
                                                   a->qrepr == RL_QREPR_F64, a->kp.ucb_pack);
+            // tables that cannot fit are rejected here, before the occupancy query below
+            // would ask the runtime for an impossible carve (and leave its error behind)
+            if (base > 160 * 1024) return lds_guard_fail(base);
             // the groups that can be resident at all: the kernel's register-limited
             // occupancy (without the pair slots), not only the 32-wave cap — cfg 4 at
             // 2^19 lanes on one GPU runs 4 groups per CU (128 VGPRs), so each may
@@ -699,7 +748,7 @@ int agent_select_kernel(rl_agent *a) {
             a->smem_v[epi] = shared_smem_bytes(a->eh.kenv, a->cfg.agent, a->cfg.policy, a->cfg.selector,
                                                a->cfg.algo, a->S, a->A, a->eh.dev_n_start(), a->block.x,
                                                a->trc_kb_v[epi], a->qrepr == RL_QREPR_F64, a->kp.ucb_pack);
-            if (a->smem_v[epi] > 160 * 1024) return fail(RL_E_ARG, "learner-group tables exceed the 160 KiB LDS");
+            if (a->smem_v[epi] > 160 * 1024) return lds_guard_fail(a->smem_v[epi]);
         }
         const int ep = a->kp.episodic ? 1 : 0;
         a->kp.trc_kb = a->trc_kb_v[ep];
@@ -1292,22 +1341,24 @@ int rl_obs_from_reference(int32_t env_kind, uint64_t obs, uint32_t *dense_state)
     return RL_OK;
 }
 
-int rl_map_register(const char *const *rows, uint32_t n_rows, int32_t *map_id) {
+// rl_map_register / rl_map_register_wide: one validation and one registry; `cap` is
+// the format's cell limit and `cap_name` its name in the messages
+static int map_register(const char *const *rows, uint32_t n_rows, int32_t *map_id, size_t cap, const char *cap_name,
+                        bool wide) {
     if (!rows || !map_id) return fail(RL_E_ARG, "null argument");
     if (n_rows == 0) return fail(RL_E_ARG, "a map needs at least one row");
     Grid g;
     for (uint32_t r = 0; r < n_rows; ++r) {
         if (!rows[r]) return fail(RL_E_ARG, "null map row " + std::to_string(r));
         // the length is bounded while it is measured: a row is never read past the cell limit
-        const size_t len = strnlen(rows[r], (size_t)RL_MAP_MAX_CELLS + 1);
+        const size_t len = strnlen(rows[r], cap + 1);
         if (len == 0) return fail(RL_E_ARG, "map row " + std::to_string(r) + " has zero columns");
         if (r > 0 && len != g[0].size())
             return fail(RL_E_ARG, "ragged map: row " + std::to_string(r) + " has " +
-                                      (len > RL_MAP_MAX_CELLS ? "more than " + std::to_string(RL_MAP_MAX_CELLS)
-                                                              : std::to_string(len)) +
+                                      (len > cap ? "more than " + std::to_string(cap) : std::to_string(len)) +
                                       " columns, row 0 has " + std::to_string(g[0].size()));
-        if ((size_t)n_rows * len > RL_MAP_MAX_CELLS)
-            return fail(RL_E_ARG, "map has more than RL_MAP_MAX_CELLS (" + std::to_string(RL_MAP_MAX_CELLS) + ") cells");
+        if ((size_t)n_rows * len > cap)
+            return fail(RL_E_ARG, std::string("map has more than ") + cap_name + " (" + std::to_string(cap) + ") cells");
         for (size_t i = 0; i < len; ++i) {
             const char ch = rows[r][i];
             if (ch != 'S' && ch != 'F' && ch != 'H' && ch != 'G')
@@ -1318,11 +1369,31 @@ int rl_map_register(const char *const *rows, uint32_t n_rows, int32_t *map_id) {
     }
     std::lock_guard<std::mutex> lock(g_map_mu);
     std::vector<Grid> &maps = map_registry();
+    std::vector<uint8_t> &flags = map_wide_flags();
     for (size_t i = 2; i < maps.size(); ++i)
-        if (maps[i] == g) { *map_id = (int32_t)i; return RL_OK; }
+        if (maps[i] == g && (flags[i] != 0) == wide) { *map_id = (int32_t)i; return RL_OK; }
     if (maps.size() >= (size_t)INT32_MAX) return fail(RL_E_ARG, "map registry full");
     maps.push_back(std::move(g));
+    flags.push_back(wide ? 1 : 0);
     *map_id = (int32_t)(maps.size() - 1);
+    return RL_OK;
+}
+
+int rl_map_register(const char *const *rows, uint32_t n_rows, int32_t *map_id) {
+    return map_register(rows, n_rows, map_id, RL_MAP_MAX_CELLS, "RL_MAP_MAX_CELLS", false);
+}
+
+int rl_map_register_wide(const char *const *rows, uint32_t n_rows, int32_t *map_id) {
+    return map_register(rows, n_rows, map_id, RL_MAP_WIDE_MAX_CELLS, "RL_MAP_WIDE_MAX_CELLS", true);
+}
+
+int rl_map_is_wide(int32_t map_id, int32_t *wide) {
+    if (!wide) return fail(RL_E_ARG, "null argument");
+    Grid g;
+    bool w = false;
+    if (!map_lookup(map_id, g, &w))
+        return fail(RL_E_ARG, "unknown FrozenLake map id " + std::to_string(map_id));
+    *wide = w ? 1 : 0;
     return RL_OK;
 }
 
@@ -1359,7 +1430,7 @@ int rl_env_table(const rl_env_config *cfg, double *prob, uint32_t *next, double 
     if (e.kind == RL_ENV_BLACKJACK) return fail(RL_E_ARG, "Blackjack has no transition table");
     for (uint32_t s = 0; s < e.S; ++s)
         for (uint32_t a = 0; a < e.A; ++a) {
-            const uint32_t w = e.trans[s * e.A + a];
+            const uint32_t w = env_wide(e.kenv) ? 0u : e.trans[s * e.A + a];
             const size_t k = ((size_t)s * e.A + a) * 3;
             double pr[3] = {1.0, 0.0, 0.0};
             uint32_t nx[3] = {0, 0, 0};
@@ -1368,13 +1439,27 @@ int rl_env_table(const rl_env_config *cfg, double *prob, uint32_t *next, double 
             if (e.kind == RL_ENV_FROZEN_LAKE || e.kind == RL_ENV_FROZEN_LAKE_EDITED) {
                 const bool edited = e.kind == RL_ENV_FROZEN_LAKE_EDITED;
                 const char cell = e.map[s / e.ncol][s % e.ncol];
-                const int n = (w >> 24) & 1 ? 3 : 1;
-                for (int i = 0; i < n; ++i) {
-                    const uint32_t o = (w >> (8 * i)) & 0xffu;
-                    pr[i] = n == 3 ? 1.0 / 3.0 : 1.0;
-                    nx[i] = o & 63u;
-                    rw[i] = edited ? ((o & 64u) ? 10.0 : -1.0) : ((o & 64u) ? 1.0 : 0.0);
-                    tm[i] = (o & 128u) ? 1 : 0;
+                if (env_wide(e.kenv)) {
+                    // the wide words as the device steps them: direction (a + 3 + i) & 3 on
+                    // a slippery map, a on a deterministic one; one outcome on 'G' / 'H'
+                    const uint16_t *t16 = (const uint16_t *)e.trans.data();
+                    const int n = (e.slippery && cell != 'G' && cell != 'H') ? 3 : 1;
+                    for (int i = 0; i < n; ++i) {
+                        const uint32_t o = t16[(size_t)s * 4 + (n == 3 ? ((a + 3u + (uint32_t)i) & 3u) : a)];
+                        pr[i] = n == 3 ? 1.0 / 3.0 : 1.0;
+                        nx[i] = o & WIDE_NEXT_MASK;
+                        rw[i] = edited ? ((o & WIDE_REWARD) ? 10.0 : -1.0) : ((o & WIDE_REWARD) ? 1.0 : 0.0);
+                        tm[i] = (o & WIDE_TERM) ? 1 : 0;
+                    }
+                } else {
+                    const int n = (w >> 24) & 1 ? 3 : 1;
+                    for (int i = 0; i < n; ++i) {
+                        const uint32_t o = (w >> (8 * i)) & 0xffu;
+                        pr[i] = n == 3 ? 1.0 / 3.0 : 1.0;
+                        nx[i] = o & 63u;
+                        rw[i] = edited ? ((o & 64u) ? 10.0 : -1.0) : ((o & 64u) ? 1.0 : 0.0);
+                        tm[i] = (o & 128u) ? 1 : 0;
+                    }
                 }
                 if (cell == 'G' || cell == 'H') rw[0] = 0.0;   // (1.0, s, 0.0, true) rows: never stepped from
             } else if (e.kind == RL_ENV_CLIFF_WALKING) {

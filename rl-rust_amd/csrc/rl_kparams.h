@@ -32,10 +32,24 @@ constexpr uint32_t ACC_CLAMP = 8, ACC_SAT = 9;
 // cells (rl_device.h EnvDev<ENV_FL_MAP>).  The built-in maps keep the kernels of
 // RL_ENV_FROZEN_LAKE / RL_ENV_FROZEN_LAKE_EDITED, whose reset is the constant 0.
 constexpr int ENV_FL_MAP = 16, ENV_FLE_MAP = 17;
-__host__ __device__ constexpr bool env_fl_plain(int e) { return e == RL_ENV_FROZEN_LAKE || e == ENV_FL_MAP; }
-__host__ __device__ constexpr bool env_fl_edited(int e) { return e == RL_ENV_FROZEN_LAKE_EDITED || e == ENV_FLE_MAP; }
+// Wide maps (rl_map_register_wide, up to RL_MAP_WIDE_MAX_CELLS cells): the same
+// start variant over the wide transition table — one u16 per (state, direction),
+// bits 0-9 next state, bit 10 reward bit, bit 11 terminated (rl_device.h
+// EnvDevWide) — where the packed outcome byte's 6-bit next state ends at 64 cells.
+constexpr int ENV_FL_WIDE = 18, ENV_FLE_WIDE = 19;
+constexpr uint32_t WIDE_NEXT_MASK = 1023u, WIDE_REWARD = 1u << 10, WIDE_TERM = 1u << 11;
+__host__ __device__ constexpr bool env_wide(int e) { return e == ENV_FL_WIDE || e == ENV_FLE_WIDE; }
+__host__ __device__ constexpr bool env_fl_plain(int e) {
+    return e == RL_ENV_FROZEN_LAKE || e == ENV_FL_MAP || e == ENV_FL_WIDE;
+}
+__host__ __device__ constexpr bool env_fl_edited(int e) {
+    return e == RL_ENV_FROZEN_LAKE_EDITED || e == ENV_FLE_MAP || e == ENV_FLE_WIDE;
+}
 __host__ __device__ constexpr bool env_fl_family(int e) { return env_fl_plain(e) || env_fl_edited(e); }
-__host__ __device__ constexpr bool env_map_start(int e) { return e == ENV_FL_MAP || e == ENV_FLE_MAP; }
+__host__ __device__ constexpr bool env_map_start(int e) { return e == ENV_FL_MAP || e == ENV_FLE_MAP || env_wide(e); }
+// u32 words of the env's transition table as the kernels copy it: one word per
+// (s, a), or for a wide map two u16 (s, direction) entries per word (A = 4)
+__host__ __device__ constexpr uint32_t trans_words(int e, uint32_t SA) { return env_wide(e) ? SA / 2u : SA; }
 // the start list of a registered map with two or more 'S' cells, one buffer:
 // [n_start f64 running sums][n_start u32 cells] (HBM; the shared kernels copy it to LDS)
 __host__ __device__ constexpr uint32_t start_list_bytes(uint32_t n_start) { return n_start * 12u; }
@@ -124,7 +138,7 @@ struct KParams {
     uint32_t n_in, n_hidden, n_params;
     int32_t act1, act2;    // rl_activation of the hidden / output layer
     // env tables
-    const uint32_t *trans; // [S][A] packed
+    const uint32_t *trans; // [S][A] packed (wide maps: u16 [S][4 directions], trans_words above)
     const double *start_cdf;   // [n_start] running sums (categorical_sample); HBM.  Registered maps:
                                // the start list (start_list_bytes above), n_start = its cells
     uint32_t n_start;

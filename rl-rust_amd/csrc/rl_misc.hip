@@ -12,6 +12,8 @@ train_launch_fn train_table_blackjack(int, int, int, int, int);
 train_launch_fn train_table_frozen_lake_edited(int, int, int, int, int);
 train_launch_fn train_table_frozen_lake_map(int, int, int, int, int);
 train_launch_fn train_table_frozen_lake_edited_map(int, int, int, int, int);
+train_launch_fn train_table_frozen_lake_wide(int, int, int, int, int);
+train_launch_fn train_table_frozen_lake_edited_wide(int, int, int, int, int);
 
 train_launch_fn lookup_train(int env, int agent, int policy, int sel, int algo, int priv) {
     switch (env) {
@@ -22,6 +24,8 @@ train_launch_fn lookup_train(int env, int agent, int policy, int sel, int algo, 
     case RL_ENV_FROZEN_LAKE_EDITED: return train_table_frozen_lake_edited(agent, policy, sel, algo, priv);
     case ENV_FL_MAP: return train_table_frozen_lake_map(agent, policy, sel, algo, priv);
     case ENV_FLE_MAP: return train_table_frozen_lake_edited_map(agent, policy, sel, algo, priv);
+    case ENV_FL_WIDE: return train_table_frozen_lake_wide(agent, policy, sel, algo, priv);
+    case ENV_FLE_WIDE: return train_table_frozen_lake_edited_wide(agent, policy, sel, algo, priv);
     }
     return nullptr;
 }
@@ -559,6 +563,8 @@ void launch_env_reset(int env, const KParams &p, hipStream_t s, uint64_t *obs) {
     case RL_ENV_FROZEN_LAKE_EDITED: hipLaunchKernelGGL(k_env_reset<RL_ENV_FROZEN_LAKE_EDITED>, g, b, 0, s, p, obs); break;
     case ENV_FL_MAP: hipLaunchKernelGGL(k_env_reset<ENV_FL_MAP>, g, b, 0, s, p, obs); break;
     case ENV_FLE_MAP: hipLaunchKernelGGL(k_env_reset<ENV_FLE_MAP>, g, b, 0, s, p, obs); break;
+    case ENV_FL_WIDE: hipLaunchKernelGGL(k_env_reset<ENV_FL_WIDE>, g, b, 0, s, p, obs); break;
+    case ENV_FLE_WIDE: hipLaunchKernelGGL(k_env_reset<ENV_FLE_WIDE>, g, b, 0, s, p, obs); break;
     }
 }
 void launch_env_step(int env, const KParams &p, hipStream_t s, const uint32_t *act, uint64_t *obs,
@@ -572,6 +578,8 @@ void launch_env_step(int env, const KParams &p, hipStream_t s, const uint32_t *a
     case RL_ENV_FROZEN_LAKE_EDITED: hipLaunchKernelGGL(k_env_step<RL_ENV_FROZEN_LAKE_EDITED>, g, b, 0, s, p, act, obs, rew, term); break;
     case ENV_FL_MAP: hipLaunchKernelGGL(k_env_step<ENV_FL_MAP>, g, b, 0, s, p, act, obs, rew, term); break;
     case ENV_FLE_MAP: hipLaunchKernelGGL(k_env_step<ENV_FLE_MAP>, g, b, 0, s, p, act, obs, rew, term); break;
+    case ENV_FL_WIDE: hipLaunchKernelGGL(k_env_step<ENV_FL_WIDE>, g, b, 0, s, p, act, obs, rew, term); break;
+    case ENV_FLE_WIDE: hipLaunchKernelGGL(k_env_step<ENV_FLE_WIDE>, g, b, 0, s, p, act, obs, rew, term); break;
     }
 }
 

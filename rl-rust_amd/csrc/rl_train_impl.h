@@ -51,9 +51,11 @@ __host__ __device__ inline uint32_t bj_dense(uint32_t row) {      // LDS row -> 
     return ((p << 5) + d) * 2u + (row & 1u);
 }
 // Pair traces on small tables (FrozenLake, CliffWalking: S*A <= 256, so a pair id
-// is 8 bits) keep every wave's visited pairs in one pool (pair_pool below)
+// is 8 bits) keep every wave's visited pairs in one pool (pair_pool below).  A wide
+// map (S*A up to 4096) fits neither the 8-bit id nor the register bitmap: it runs
+// the per-lane u16 pair lists, as Taxi does.
 __host__ __device__ constexpr bool pair_pool_env(int env) {
-    return env == RL_ENV_CLIFF_WALKING || env_fl_family(env);
+    return env == RL_ENV_CLIFF_WALKING || (env_fl_family(env) && !env_wide(env));
 }
 // Fixed-point single-table Q-learning (rl_device.h argmax_max, the fused argmax +
 // max of the target row) keeps an f64 image of every entry beside its int64 word:
@@ -83,7 +85,8 @@ __host__ __device__ constexpr bool qsh_layout(int fq, int ucb, int P, int algo) 
 //   n/t  UCB counters (u64 [S][A], u64 t);  list u16 touched rows + count (traces)
 //   rcp  f64 [nthr+1]   1.0/n for the combination rule (mean_delta)
 //   tr   env transition table (FrozenLake / CliffWalking; Taxi computes its
-//        transitions and reads its start cdf from HBM, Blackjack has none)
+//        transitions and reads its start cdf from HBM, Blackjack has none);
+//        u32 [S][A], or a wide map's u16 [S][4] (rl_kparams.h trans_words)
 //   trc  pair traces (traces == 2): the first trc_cap slots of every lane's pair
 //        list, ids u16 [cap][nthr] then E f64 [cap][nthr] (column = thread);
 //        small tables: the first trc_cap items of every wave's pair pool, tags
@@ -125,7 +128,7 @@ __host__ __device__ inline SmemLayout smem_layout(int env, int P, int ucb, int t
     l.t = off; off += (shared_q && ucb) ? (ucb == 2 ? 32u : 16u) : 0u;   // T[0], T[1] (+ ARR: UCB + ES)
     l.list = off; off += (shared_q && traces) ? align16(PSA * 2u) + 16u : 0u;
     l.rcp = off; off += align16(l.nrcp * 8u);
-    l.tr = off; off += (env == RL_ENV_TAXI || env == RL_ENV_BLACKJACK) ? 0u : align16(SA * 4u);
+    l.tr = off; off += (env == RL_ENV_TAXI || env == RL_ENV_BLACKJACK) ? 0u : align16(trans_words(env, SA) * 4u);
     // start distributions: FrozenLake's built-in maps start at 0 (fixed_start), Taxi
     // probes the HBM cdf (taxi_start), CliffWalking / Blackjack have none; a registered
     // FrozenLake map with two or more 'S' cells keeps its start list here in the
@@ -604,8 +607,11 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
             if constexpr (SPEC) *(uint32_t *)(T + 2) = 0u;
         }
     }
-    if constexpr (ENV != RL_ENV_TAXI && ENV != RL_ENV_BLACKJACK)
+    if constexpr (env_wide(ENV)) {       // u16 [S][4 directions]: the index map is Q's (rows of A = 4)
+        for (uint32_t i = tid; i < SA; i += nthr) ((uint16_t *)TR)[lds_of(i)] = ((const uint16_t *)p.trans)[i];
+    } else if constexpr (ENV != RL_ENV_TAXI && ENV != RL_ENV_BLACKJACK) {
         for (uint32_t i = tid; i < SA; i += nthr) TR[lds_of(i)] = p.trans[i];
+    }
     // registered map: the start list as u32 words (8-byte aligned: l.cdf is a multiple of 16)
     if constexpr (env_map_start(ENV))
         for (uint32_t i = tid; i < p.n_start * 3u; i += nthr)
@@ -1056,7 +1062,11 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
                 doS = alive;
             }
         }
-        if constexpr (env_fl_family(ENV)) {
+        if constexpr (env_wide(ENV)) {             // the table entry is read behind the draw
+            uint32_t pos = L.s;
+            fl_advance_wide<env_fl_edited(ENV), SLIP, LDS_AM>(doR, doS, pos, L.z, L.a, L.rng, tabs, s2, r, term);
+            L.ready = doR ? true : (term ? false : L.ready);
+        } else if constexpr (env_fl_family(ENV)) {
             uint32_t pos = L.s;                    // reset or step in one predicated block
             const uint32_t w = tabs.trans[tidx<LDS_AM, 4>(tabs, L.s, L.a)];
             fl_advance<env_fl_edited(ENV), SLIP, LDS_AM, env_map_start(ENV)>(doR, doS, pos, L.z, w, L.rng, tabs, s2,
@@ -1798,7 +1808,7 @@ __global__ void __launch_bounds__(256) k_train_private(KParams p) {
     const uint32_t tid = threadIdx.x, nthr = blockDim.x;
     if (tid < STATS_W) ACC[tid] = 0ull;
     if constexpr (ENV != RL_ENV_TAXI && ENV != RL_ENV_BLACKJACK)
-        for (uint32_t i = tid; i < SA; i += nthr) TR[i] = p.trans[i];
+        for (uint32_t i = tid; i < trans_words(ENV, SA); i += nthr) TR[i] = p.trans[i];
     __syncthreads();
 
     EnvTables tabs;
@@ -1842,7 +1852,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     const uint32_t tid = threadIdx.x, nthr = blockDim.x;
     if (tid < STATS_W) ACC[tid] = 0ull;
     if constexpr (ENV != RL_ENV_TAXI && ENV != RL_ENV_BLACKJACK)
-        for (uint32_t i = tid; i < SA; i += nthr) TR[i] = p.trans[i];
+        for (uint32_t i = tid; i < trans_words(ENV, SA); i += nthr) TR[i] = p.trans[i];
     __syncthreads();
 
     EnvTables tabs;
@@ -1896,7 +1906,7 @@ __global__ void __launch_bounds__(256) k_train_private_lds(KParams p) {
     const uint32_t nv = lane0 + nl <= p.L ? nl : (uint32_t)(p.L - lane0);   // lanes of this block
     if (tid < STATS_W) ACC[tid] = 0ull;
     if constexpr (ENV != RL_ENV_TAXI && ENV != RL_ENV_BLACKJACK)
-        for (uint32_t i = tid; i < SA; i += nthr) TR[i] = p.trans[i];
+        for (uint32_t i = tid; i < trans_words(ENV, SA); i += nthr) TR[i] = p.trans[i];
     const double *qg = p.q_priv + lane0 * PSA;                   // the block's tables, contiguous
     for (uint32_t l = 0; l < nv; ++l)
         for (uint32_t e = tid; e < PSA; e += nthr) QS[l * stride + e] = qg[(uint64_t)l * PSA + e];

@@ -99,6 +99,8 @@ SIGNATURES = {
     "rl_blackjack_obs_id": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "rl_obs_to_reference": (C.c_uint64, [C.c_int32, C.c_uint32]),
     "rl_map_register": (C.c_int, [_P(C.c_char_p), C.c_uint32, _P(C.c_int32)]),
+    "rl_map_register_wide": (C.c_int, [_P(C.c_char_p), C.c_uint32, _P(C.c_int32)]),
+    "rl_map_is_wide": (C.c_int, [C.c_int32, _P(C.c_int32)]),
     "rl_map_info": (C.c_int, [C.c_int32, _P(C.c_uint32), _P(C.c_uint32), _V, C.c_size_t]),
     "rl_env_dims": (C.c_int, [_P(EnvConfig), _P(C.c_uint32), _P(C.c_uint32)]),
     "rl_env_table": (C.c_int, [_P(EnvConfig), _V, _V, _V, _V, _V]),
@@ -222,17 +224,28 @@ def env_config(p):
 
 
 MAP_MAX_CELLS = 64    # rl.h RL_MAP_MAX_CELLS
+MAP_WIDE_MAX_CELLS = 1024    # rl.h RL_MAP_WIDE_MAX_CELLS
 
 
-def register_map(rows):
+def register_map(rows, wide=False):
     """FrozenLakeEnv::new / FrozenLakeEditedEnv::new with the caller's map (rl.h
     rl_map_register): rows of equal length over S, F, H, G.  Returns the id to put in
-    `map8x8` (>= 2; the same rows give the same id again)."""
+    `map8x8` (>= 2; the same rows give the same id again).  wide=True registers the
+    wide table format (rl_map_register_wide: up to MAP_WIDE_MAX_CELLS cells, an id of
+    its own)."""
     rows = [r.encode() if isinstance(r, str) else bytes(r) for r in rows]
     arr = (C.c_char_p * max(len(rows), 1))(*rows)
     mid = C.c_int32(-1)
-    check(lib().rl_map_register(arr, len(rows), C.byref(mid)))
+    fn = lib().rl_map_register_wide if wide else lib().rl_map_register
+    check(fn(arr, len(rows), C.byref(mid)))
     return mid.value
+
+
+def map_is_wide(map_id):
+    """True for an id from register_map(rows, wide=True)"""
+    w = C.c_int32(-1)
+    check(lib().rl_map_is_wide(map_id, C.byref(w)))
+    return bool(w.value)
 
 
 def map_info(map_id):
@@ -247,10 +260,15 @@ def map_info(map_id):
 
 def default_params(**kw):
     """Reference CLI defaults (src/bin/frozen_lake.rs:35-73; decay rule :84).
-    map=rows registers the caller's FrozenLake map and sets its id in `map8x8`."""
-    if "map" in kw:
+    map=rows registers the caller's FrozenLake map and sets its id in `map8x8`;
+    with wide=True in the wide table format."""
+    if "map" in kw or "wide" in kw:
         kw = dict(kw)
-        kw["map8x8"] = register_map(kw.pop("map"))
+        wide = bool(kw.pop("wide", False))
+        if "map" in kw:
+            kw["map8x8"] = register_map(kw.pop("map"), wide=wide)
+        elif wide:
+            raise ValueError("wide=True needs map=rows")
     p = dict(env="frozen_lake", map8x8=0, slippery=0, max_steps=100, agent="one_step",
              policy="tabular", selector="eps_greedy", algo="qlearning", decay_kind=0,
              lr=0.05, gamma=0.95, lambda_=0.5, eps0=1.0, n_episodes_for_decay=100000,
