@@ -8,6 +8,9 @@ north-star bound |dQ| < 1e-5 is asserted too, as a floor).
 import numpy as np
 import pytest
 
+import coverage as cov
+import matrix_cases as mc
+
 pytestmark = pytest.mark.gpu
 
 INT_FIELDS = ["s", "s2", "a", "a2", "term", "mode"]
@@ -47,6 +50,47 @@ def _assert_q_equal(dq, rq):
     fin = np.isfinite(dq) & np.isfinite(rq)
     assert np.max(np.abs(dq[fin] - rq[fin]), initial=0.0) < 1e-5
     assert np.array_equal(dq[~nan_d].view(np.uint64), rq[~nan_d].view(np.uint64))
+
+
+def _case_kw(case):
+    """a case's parameters without its options (ucb_preset: preset UCB counters)"""
+    return {k: v for k, v in case.items() if k != "ucb_preset"}
+
+
+def _preset_ucb(case, *objs):
+    """UCB + expected SARSA from fresh counters compares NaN with NaN (SURVEY F7);
+    a case with ucb_preset starts both sides from counts in [1, 50), t = 5000"""
+    if case.get("ucb_preset"):
+        for o in objs:
+            o.set_ucb(*mc.ucb_preset(o.S, o.A))
+
+
+def _oracle_is_live(ref, recs, p, **need):
+    """coverage conditions of a live sibling (tests/coverage.py), on the ORACLE's
+    records: the shared-matrix minima and at least one terminal or truncated training
+    step, unless the case states its own"""
+    m = cov.measure(recs, p["group_size"], p["q_default"], q=ref.q(), sync_every=p["sync_every"])
+    cov.assert_live(m, **{**mc.SHARED_NEED, "resets": p["n_lanes"], "terminals": 1, **need})
+    return m
+
+
+# The live siblings of the tests below and the shapes those tests run at, in one place:
+# tests/test_matrix_coverage.py measures the same cases on the oracle without a GPU.
+FL8_Q_LIVE = dict(env="frozen_lake", map8x8=1, algo="qlearning", group_size=256, q_default=0.25)
+LPW_SHAPE = dict(n_lanes=1000, sync_every=16, launches=4)
+LPW_LIVE = FL8_Q_LIVE
+THROUGHPUT_SHAPE = dict(n_lanes=1500, sync_every=16, launches=5)
+THROUGHPUT_LIVE = [FL8_Q_LIVE,
+                   dict(env="taxi", selector="ucb", algo="expected_sarsa", group_size=128, ucb_preset=True)]
+RESET_STEP_SHAPE = dict(n_lanes=500, sync_every=16, launches=5)
+RESET_STEP_LIVE = FL8_Q_LIVE
+TINY_SHAPE = dict(sync_every=16, launches=6)
+# (n_lanes, group_size, case, conditions of its own).  One lane shares no entry with
+# another and cannot be changed by two groups: it must move entries with every step
+# instead (93 steps move 49 entries on the oracle)
+TINY_LIVE = [(1, 64, dict(env="frozen_lake", map8x8=1, algo="qlearning", q_default=0.25),
+              dict(multi_contrib=0, entries_changed=6)),
+             (65, 64, dict(env="taxi", selector="ucb", algo="expected_sarsa", ucb_preset=True), {})]
 
 
 def test_kat_rng(rl, oracle):
@@ -208,24 +252,49 @@ SHARED_CASES = [
     # and UCB without expected SARSA (no barrier after the counter increments)
     dict(env="taxi", agent="traces", selector="ucb", algo="expected_sarsa", group_size=256),
     dict(env="cliff_walking", agent="traces", selector="ucb", algo="sarsa", group_size=64),
-    # owner-form settle with > 64 contributions per entry: 1.0/n by division
+    # owner form, group of 200: at most 59 contributions land on one entry (the first
+    # step gives about G / 4), so 1.0/n stays in the table of reciprocals; the division
+    # path (> 64 per entry) is reached by SHARED_LIVE_CASES' groups of 512
     dict(env="frozen_lake", map8x8=1, algo="sarsa", group_size=200),
 ]
 
+# Live siblings: with q_default 0 FrozenLake pays nothing before the goal, so the
+# rows above move one or two Q entries in 55 000 steps, and UCB + expected SARSA
+# from fresh counters is NaN throughout.  q_default 0.25 (exact in the fixed point)
+# and preset counters give the same kernels non-zero finite TD errors; the oracle's
+# records must show it (tests/coverage.py), here and in tests/test_matrix_coverage.py.
+# (case, n_lanes, sync_every, launches, extra coverage conditions)
+SHARED_LIVE_CASES = [
+    (dict(env="frozen_lake", map8x8=1, algo="qlearning", group_size=256, q_default=0.25), 600, 16, 6, {}),
+    (dict(env="frozen_lake", map8x8=1, slippery=1, algo="expected_sarsa", group_size=64, q_default=0.25),
+     600, 16, 6, {}),
+    (dict(env="frozen_lake", map8x8=1, algo="sarsa", group_size=200, q_default=0.25), 600, 16, 6, {}),
+    # Taxi's drop-off is rare in 96 steps: max_steps 6 (the matrix's) ends episodes, by
+    # truncation, inside the recorded window
+    (dict(env="taxi", selector="ucb", algo="expected_sarsa", group_size=128, max_steps=6, ucb_preset=True),
+     600, 16, 6, {}),
+    (dict(env="taxi", agent="traces", selector="ucb", algo="expected_sarsa", group_size=256, max_steps=6,
+          ucb_preset=True), 600, 16, 6, {}),
+    # owner-form settle with > 64 contributions per entry: 1.0/n by division
+    (dict(env="frozen_lake", map8x8=1, algo="sarsa", group_size=512, q_default=0.25), 1100, 8, 4,
+     dict(max_contrib=65)),
+    (dict(env="cliff_walking", algo="sarsa", group_size=512, q_default=0.25), 1100, 8, 4, dict(max_contrib=65)),
+]
 
-@pytest.mark.parametrize("case", SHARED_CASES, ids=lambda c: "-".join(f"{v}" for v in c.values()))
-def test_shared_mode_matches_batched_oracle(rl, oracle, case):
-    """Learner groups in LDS + merge every K steps: bit-exact vs the oracle's
-    batched schedule (raw fixed-point Q, UCB counters, streams)."""
-    L = 600
-    p = _params(rl, n_lanes=L, sync_every=16, n_episodes_for_decay=40, **case)
+
+def _run_shared_case(rl, oracle, case, L=600, sync_every=16, launches=6, need=None):
+    p = _params(rl, n_lanes=L, sync_every=sync_every, n_episodes_for_decay=40, **_case_kw(case))
     dev = rl.Agent(p)
     dev.set_recording(True)
     ref = oracle.Batch(p)
     ref.set_record(True)
-    dev.run(6)
-    ref.run(6)
-    _assert_records_equal(dev.records(), ref.records())
+    _preset_ucb(case, dev, ref)
+    dev.run(launches)
+    ref.run(launches)
+    ref_recs = ref.records()
+    if need is not None:
+        _oracle_is_live(ref, ref_recs, p, **need)
+    _assert_records_equal(dev.records(), ref_recs)
     assert np.array_equal(dev.q_raw(), ref.q_raw())
     _assert_q_equal(dev.q(), ref.q())
     if case.get("selector") == "ucb":
@@ -238,6 +307,21 @@ def test_shared_mode_matches_batched_oracle(rl, oracle, case):
     _assert_records_equal(dev.records(), ref.records())
     assert np.array_equal(dev.q_raw(), ref.q_raw())
     _assert_stats_equal(dev, ref)
+
+
+@pytest.mark.parametrize("case", SHARED_CASES, ids=lambda c: "-".join(f"{v}" for v in c.values()))
+def test_shared_mode_matches_batched_oracle(rl, oracle, case):
+    """Learner groups in LDS + merge every K steps: bit-exact vs the oracle's
+    batched schedule (raw fixed-point Q, UCB counters, streams)."""
+    _run_shared_case(rl, oracle, case)
+
+
+@pytest.mark.parametrize("case,L,K,launches,need", SHARED_LIVE_CASES,
+                         ids=["-".join(f"{v}" for v in c[0].values()) for c in SHARED_LIVE_CASES])
+def test_shared_mode_live_siblings_match_batched_oracle(rl, oracle, case, L, K, launches, need):
+    """The same comparison on cases whose oracle records are live (non-zero finite TD
+    errors, moving entries, shared contributions): asserted before the device is compared."""
+    _run_shared_case(rl, oracle, case, L=L, sync_every=K, launches=launches, need=need)
 
 
 def test_full_size_fl8x8_properties(rl):
@@ -346,17 +430,23 @@ def test_dyna_matches_oracle(rl, oracle, case):
 
 @pytest.mark.parametrize("lpw", ["64", "32", "16"])
 @pytest.mark.parametrize("case", [dict(env="cliff_walking", agent="traces", algo="sarsa", group_size=200),
-                                  dict(env="frozen_lake", map8x8=1, algo="qlearning", group_size=256)],
-                         ids=["cw-traces", "fl-q"])
+                                  dict(env="frozen_lake", map8x8=1, algo="qlearning", group_size=256),
+                                  LPW_LIVE],
+                         ids=["cw-traces", "fl-q", "fl-q-live"])
 def test_lanes_per_wave_mapping(rl, oracle, case, lpw, monkeypatch):
     """Learner groups spread over more waves (16 / 32 lanes per wave, the
     layout small grids get) give the same results as 64 lanes per wave."""
     monkeypatch.setenv("RLAMD_LPW", lpw)
-    p = _params(rl, n_lanes=1000, sync_every=16, n_episodes_for_decay=40, **case)
+    p = _params(rl, n_lanes=LPW_SHAPE["n_lanes"], sync_every=LPW_SHAPE["sync_every"], n_episodes_for_decay=40,
+                **case)
     dev = rl.Agent(p)
     ref = oracle.Batch(p)
-    dev.run(4)
-    ref.run(4)
+    live = case is LPW_LIVE
+    ref.set_record(live)
+    dev.run(LPW_SHAPE["launches"])
+    ref.run(LPW_SHAPE["launches"])
+    if live:
+        _oracle_is_live(ref, ref.records(), p)
     assert np.array_equal(dev.q_raw(), ref.q_raw())
     _assert_stats_equal(dev, ref)
 
@@ -401,16 +491,24 @@ def test_device_matches_golden_cfg1_faithful_loop(rl):
 @pytest.mark.parametrize("L,G,kw", [(1, 64, dict(env="frozen_lake", map8x8=1, algo="qlearning")),
                                     (65, 64, dict(env="taxi", selector="ucb", algo="expected_sarsa")),
                                     (3, 256, dict(env="cliff_walking", agent="traces", algo="sarsa")),
-                                    (130, 129, dict(env="blackjack", policy="double", algo="sarsa"))],
-                         ids=["fl-L1", "taxi-L65-G64", "cw-traces-L3", "bj-L130-G129"])
+                                    (130, 129, dict(env="blackjack", policy="double", algo="sarsa")),
+                                    TINY_LIVE[0][:3], TINY_LIVE[1][:3]],
+                         ids=["fl-L1", "taxi-L65-G64", "cw-traces-L3", "bj-L130-G129", "fl-L1-live",
+                              "taxi-L65-G64-live"])
 def test_tiny_and_ragged_groups(rl, oracle, L, G, kw):
     """Edge sizes: one lane, a group larger than the lane count, a last group
     with a single lane, a group size that is not a multiple of 64."""
-    p = _params(rl, n_lanes=L, group_size=G, sync_every=16, n_episodes_for_decay=40, **kw)
+    p = _params(rl, n_lanes=L, group_size=G, sync_every=TINY_SHAPE["sync_every"], n_episodes_for_decay=40,
+                **_case_kw(kw))
     dev = rl.Agent(p)
     ref = oracle.Batch(p)
-    dev.run(6)
-    ref.run(6)
+    _preset_ucb(kw, dev, ref)
+    live = next((need for _, _, c, need in TINY_LIVE if c is kw), None)
+    ref.set_record(live is not None)
+    dev.run(TINY_SHAPE["launches"])
+    ref.run(TINY_SHAPE["launches"])
+    if live is not None:
+        _oracle_is_live(ref, ref.records(), p, **live)
     assert np.array_equal(dev.q_raw(), ref.q_raw())
     _assert_stats_equal(dev, ref)
 
@@ -525,16 +623,24 @@ def test_blackjack_terminal_rows_after_set_q(rl, oracle, terminal):
                                   dict(env="taxi", selector="ucb", algo="expected_sarsa", group_size=128),
                                   dict(env="blackjack", policy="double", algo="qlearning", group_size=256),
                                   dict(env="cliff_walking", agent="traces", algo="sarsa", group_size=64),
-                                  dict(env="blackjack", algo="expected_sarsa", group_size=512, q_default=0.25)],
-                         ids=["fl-q-o8", "cw-sarsa-o8", "taxi-ucb-es", "bj-double-o8", "cw-traces", "bj-es-o8"])
+                                  dict(env="blackjack", algo="expected_sarsa", group_size=512, q_default=0.25),
+                                  THROUGHPUT_LIVE[0], THROUGHPUT_LIVE[1]],
+                         ids=["fl-q-o8", "cw-sarsa-o8", "taxi-ucb-es", "bj-double-o8", "cw-traces", "bj-es-o8",
+                              "fl-q-o8-live", "taxi-ucb-es-live"])
 def test_throughput_variant_matches_oracle(rl, oracle, case):
     """The kernels the bench runs (no records, no episode log: the INSTR=false
     and occupancy-8 instantiations): raw Q, UCB counters and stats bit-exact."""
-    p = _params(rl, n_lanes=1500, sync_every=16, n_episodes_for_decay=40, **case)
+    p = _params(rl, n_lanes=THROUGHPUT_SHAPE["n_lanes"], sync_every=THROUGHPUT_SHAPE["sync_every"],
+                n_episodes_for_decay=40, **_case_kw(case))
     dev = rl.Agent(p)
     ref = oracle.Batch(p)
-    dev.run(5)
-    ref.run(5)
+    _preset_ucb(case, dev, ref)
+    live = any(case is c for c in THROUGHPUT_LIVE)
+    ref.set_record(live)                    # the oracle's records only: the device runs INSTR=false
+    dev.run(THROUGHPUT_SHAPE["launches"])
+    ref.run(THROUGHPUT_SHAPE["launches"])
+    if live:
+        _oracle_is_live(ref, ref.records(), p)
     assert np.array_equal(dev.q_raw(), ref.q_raw())
     if case.get("selector") == "ucb":
         dn, dt = dev.ucb()
@@ -667,6 +773,7 @@ RESET_STEP_CASES = [
     dict(env="blackjack", policy="double", algo="qlearning", group_size=128),   # cfg 5's kernel (o8)
     dict(env="cliff_walking", agent="traces", algo="sarsa", group_size=64),    # cfg 4's kernel
     dict(env="frozen_lake", map8x8=1, algo="qlearning", group_size=256),       # o8, sweep form
+    RESET_STEP_LIVE,                                                            # its live sibling
     dict(env="taxi", algo="expected_sarsa", group_size=100),
     dict(env="frozen_lake", map8x8=1, slippery=1, agent="traces", policy="double", algo="expected_sarsa",
          group_size=64),
@@ -678,18 +785,21 @@ def test_reset_step_schedule_matches_oracle(rl, oracle, case):
     """rl_agent_set_reset_step: a resetting lane resets, selects and steps in one
     synchronous step (kind 3 records) — device == oracle bit for bit, in run mode
     and with the eval interleave."""
-    L = 500
-    p = _params(rl, n_lanes=L, sync_every=16, n_episodes_for_decay=40, **case)
+    L = RESET_STEP_SHAPE["n_lanes"]
+    p = _params(rl, n_lanes=L, sync_every=RESET_STEP_SHAPE["sync_every"], n_episodes_for_decay=40, **case)
     dev = rl.Agent(p)
     dev.set_reset_step(True)
     dev.set_recording(True)
     ref = oracle.Batch(p)
     ref.set_reset_step(True)
     ref.set_record(True)
-    dev.run(5)
-    ref.run(5)
-    recs = dev.records()
-    _assert_records_equal(recs, ref.records())
+    dev.run(RESET_STEP_SHAPE["launches"])
+    ref.run(RESET_STEP_SHAPE["launches"])
+    recs, ref_recs = dev.records(), ref.records()
+    if case is RESET_STEP_LIVE:
+        # live sibling: a reset-and-step record takes the place of every RESET
+        _oracle_is_live(ref, ref_recs, p, resets=0, kind3=L)
+    _assert_records_equal(recs, ref_recs)
     assert (recs["kind"] == 3).any() and not (recs["kind"] == 1).any()
     assert np.array_equal(dev.q_raw(), ref.q_raw())
     _assert_stats_equal(dev, ref)
