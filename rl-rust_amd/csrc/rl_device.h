@@ -1015,6 +1015,11 @@ __device__ __forceinline__ int64_t wave_sum_i64(int64_t v) {
     for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
 }
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
 __device__ __forceinline__ uint32_t wave_or_u32(uint32_t v) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) v |= __shfl_xor(v, off, 64);

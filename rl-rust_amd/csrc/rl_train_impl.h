@@ -191,7 +191,9 @@ struct LaneRegs {
     double eps, epi_reward;
 };
 // per-launch counters (rl_stats slots 0-4); the shared kernel keeps them per
-// wave in scalar registers (ballot counts), the private kernel per lane
+// wave in scalar registers (ballot counts; LANE_CNT in train_shared_body: the
+// training steps / episodes per lane, summed after the loop), the private kernel
+// per lane
 struct Counters {
     uint32_t n_train = 0, n_eval = 0, n_tep = 0, n_eep = 0;
     int64_t rsum = 0;      // sum over finished training episodes of rint(reward * 2^16)
@@ -995,6 +997,19 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
     // wave-level per-launch counters (scalar registers: ballot popcounts)
     uint32_t c_train = 0, c_eval = 0, c_tep = 0, c_eep = 0;
     unsigned long long *const RSUM = &ACC[4];
+    // LANE_CNT: training steps and finished training episodes counted per lane instead
+    // (one v_add_u32 per step; the episodes are L.train_ep's advance over the launch)
+    // and summed over the wave after the loop.  A ballot of a bool that is no compare's
+    // own result re-materialises it first (v_cndmask + v_cmp_ne, also through
+    // __builtin_amdgcn_ballot_w64), so the two ballots cost 4 VALU per wave-step.  The
+    // per-lane form holds two more VGPRs over the loop: only for the one-step tabular
+    // eps-greedy FrozenLake kernels in the fixed point, whose 64-VGPR budget takes them
+    // (52 to 61, no scratch); the CliffWalking and Blackjack 8-wave kernels would
+    // spill (profiles/launch_fixed_cost.md §3)
+    constexpr bool LANE_CNT = ENV == RL_ENV_FROZEN_LAKE && AGENT == RL_AGENT_ONE_STEP &&
+                              POLICY == RL_POLICY_TABULAR && !UCB && !FQ;
+    uint32_t n_train = 0;
+    const uint32_t train_ep0 = L.train_ep;
 
     // Taxi: the transition word of the lane's (s, a) from the host's table (HBM, 12 KB:
     // L2-resident), read one step ahead — after the selection that fixes the next
@@ -1637,14 +1652,22 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
         } else if (INSTR && p.rec && active) {
             write_record(p, k, lane, 0u, 0u, 0u, 0u, 0u, 0.0, false, 0.0, RL_MODE_DONE);
         }
-        c_train += (uint32_t)__popcll(__ballot(train));
-        c_tep += (uint32_t)__popcll(__ballot(tr));
+        if constexpr (LANE_CNT) {
+            n_train += train ? 1u : 0u;
+        } else {
+            c_train += (uint32_t)__popcll(__ballot(train));
+            c_tep += (uint32_t)__popcll(__ballot(tr));
+        }
         if (EPI > 0 || (EPI < 0 && p.episodic)) {   // run(): lanes only train, so no eval steps / episodes
             c_eval += (uint32_t)__popcll(__ballot(doS && !train));
             c_eep += (uint32_t)__popcll(__ballot(ev));
         }
     }
 
+    if constexpr (LANE_CNT) {
+        c_train = wave_sum_u32(n_train);
+        c_tep = wave_sum_u32(L.train_ep - train_ep0);
+    }
     if (active) lane_store(p, lane, L);
     if constexpr (POOL) {
         const uint32_t nl = npool < lay.trc_cap ? npool : lay.trc_cap;

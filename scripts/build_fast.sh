@@ -13,7 +13,7 @@ mkdir -p exp
 TU=${TU:-frozen_lake}
 NAME=${NAME:-fast}
 ONLY=${ONLY:-0,0,0,1,0}
-ALL="frozen_lake cliff_walking taxi blackjack frozen_lake_edited"
+ALL="frozen_lake cliff_walking taxi blackjack frozen_lake_edited frozen_lake_map frozen_lake_edited_map frozen_lake_wide frozen_lake_edited_wide"
 SRC=${SRCDIR:-csrc}       # SRCDIR / INCDIR: a patched copy of the sources (diagnostic builds)
 INC=${INCDIR:-../include}
 F="--offload-arch=gfx950 -O3 -std=c++17 -I$INC -fPIC -ffp-contract=off -fno-fast-math -Wall -Wno-unused-result -mllvm -amdgpu-atomic-optimizer-strategy=None"
