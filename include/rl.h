@@ -399,6 +399,63 @@ int rl_agent_take_episodes(rl_agent *a, rl_episode_record *out, uint64_t cap, ui
  * aux = {eps lo, eps hi, eval episodes left, episode length}; for checkpoints and tests */
 int rl_agent_lane_state(rl_agent *a, uint32_t *core, uint32_t *aux, size_t n_lanes);
 
+/* -------- populations: M independent shared-Q agents in one launch (additive to ABI 7)
+ * The reference's bins run a sweep as one agent after another (src/bin/frozen_lake.rs:
+ * 167-175 loops agent x selector x algorithm; a user extends it over seeds and learning
+ * rates).  A population is that sweep behind one handle: M members of G lanes each, one
+ * workgroup per member and launch, and no merge — a member's group is the only writer
+ * of its table.
+ * Contract: member m is, bit for bit, the agent rl_agent_create builds alone from `base`
+ * with n_lanes = group_size = G and member m's lr, gamma, eps0, eps_decay, eps_final,
+ * ucb_c, seed and lane_offset (lane i of member m draws from stream (seed_m,
+ * lane_offset_m + i)), put through the same run / train / evaluate / reset calls: raw Q
+ * words, UCB counters and t, every lane record (rl_agent_lane_state), and the step /
+ * episode / reward counters.  The members share the env config, the agent / policy /
+ * selector / algo kinds, decay_kind, q_default, sync_every, eval_episodes and the device.
+ * One representation per population: RL_QREPR_FIXED40 iff its proof holds for every
+ * member (rl_q_repr), else RL_QREPR_F64 for all — a member then equals its lone agent
+ * after rl_agent_set_q_mode(RL_QMODE_F64); rl_agent_set_q_mode follows the same rule.
+ * train / evaluate return when every lane of every member is done; a member that is
+ * done earlier is still launched, idle: nothing of it moves.
+ * Limits (v1): 2 <= G <= 1024, M >= 1, M * G < 2^32; the one-step agent; tabular or
+ * double policy; eps-greedy or UCB; SARSA, Q-learning or expected SARSA, but not UCB
+ * with expected SARSA; FrozenLake on the built-in maps (0 / 1), CliffWalking, Taxi,
+ * Blackjack.  A learner group whose tables exceed the LDS is rejected as by
+ * rl_agent_create (Blackjack with the double policy under UCB).
+ * Errors: RL_E_ARG with a message naming the field, before any HIP call, for
+ * n_members == 0, G outside 2..1024, n_lanes != M * G, a combination outside the limits
+ * (traces, NeuralPolicy, FrozenLakeEdited, registered or wide maps, UCB + expected
+ * SARSA), a member window with m0 + n > M, a buffer length other than the stated one, a
+ * null pointer.
+ * The handle is an rl_agent.  rl_agent_destroy, _run, _synchronize, _train, _evaluate,
+ * _reset (every member back to q_default and its own fresh selector), _stats (totals
+ * over the members), _dims, _q_repr, _set_q_mode, _get_epsilon, _lane_state (M * G
+ * lanes, member-major), _occupancy, _set_timing / _get_timing and _set_stream work on
+ * it; every other rl_agent_* call returns RL_E_STATE and names the rl_population_* call
+ * to use where there is one.  The rl_population_* calls return RL_E_STATE on a handle
+ * from rl_agent_create.
+ * Out of scope: setting Q or UCB counters per member, checkpoint / resume, recording
+ * and the episode log, planning, communicators and external merges. */
+typedef struct rl_member_config {
+    double lr, gamma, eps0, eps_decay, eps_final, ucb_c;
+    uint64_t seed, lane_offset;
+} rl_member_config;
+/* base: kinds, env, decay_kind, q_default, group_size = G, sync_every, eval_episodes,
+ * device; base->n_lanes must be n_members * group_size; the base's per-member fields
+ * (lr .. ucb_c, seed, lane_offset) and lambda / net are ignored */
+int rl_population_create(const rl_agent_config *base, const rl_member_config *members,
+                         uint32_t n_members, rl_agent **out);
+int rl_population_size(rl_agent *a, uint32_t *n_members, uint32_t *lanes_per_member);
+/* members [m0, m0 + n): [member][P][S][A] values / raw words (rl_agent_get_q_raw);
+ * n_out must be n * P*S*A */
+int rl_population_get_q(rl_agent *a, uint32_t m0, uint32_t n, double *out, size_t n_out);
+int rl_population_get_q_raw(rl_agent *a, uint32_t m0, uint32_t n, int64_t *out, size_t n_out);
+/* [member][S][A] counts (n_counts = n * S*A), [member] t (n_t = n) */
+int rl_population_get_ucb(rl_agent *a, uint32_t m0, uint32_t n, uint64_t *counts, size_t n_counts,
+                          uint64_t *t, size_t n_t);
+/* one rl_stats per member (launches: the population's; done_lanes: the member's) */
+int rl_population_stats(rl_agent *a, uint32_t m0, uint32_t n, rl_stats *out);
+
 /* -------- NeuralPolicy weights (policy == RL_POLICY_NEURAL) */
 /* n_in = input features, n_params = per-lane parameter count:
  * [W1 n_in x hidden][b1 hidden][W2 hidden x COUNT][b2 COUNT], row-major

@@ -596,9 +596,29 @@ struct rl_agent {
         bool on = false;
     } peer;
     double q_abs0 = 0.0;       // shared mode: max |Q| the table was last reset / set to (delta_bound's Q0)
+    // a population (rl_population_create): M members of G lanes, member m's lanes
+    // [m*G, (m+1)*G); q_base / n_base / t_base hold M tables / counter sets / t (member-major),
+    // one representation for all of them; no merge buffers
+    bool pop = false;
+    uint32_t M = 0;
+    std::vector<rl_member_config> members;
+    MemberParams *members_d = nullptr;
+    unsigned long long *pop_stats_d = nullptr;   // [M][STATS_W]
+    pop_launch_fn pop_fn = nullptr;
+    PopParams pp{};
 };
 
 namespace {
+
+// rl_agent_* calls a population handle does not take (rl.h rl_population_create)
+int population_unsupported(const char *call, const char *instead) {
+    return fail(RL_E_STATE, std::string(call) + ": not available on a population handle" +
+                                (instead ? std::string(" (use ") + instead + ")" : std::string()));
+}
+#define POP_UNSUPPORTED(a, call, instead)                                                          \
+    do {                                                                                           \
+        if ((a) && (a)->pop) return population_unsupported(call, instead);                         \
+    } while (0)
 
 void agent_sync_params(rl_agent *a);
 // the peer-read merge's region handling (defined with the ABI 7 calls below)
@@ -614,7 +634,31 @@ int lds_guard_fail(size_t need) {
                               " bytes needed, " + std::to_string(160 * 1024) + " available)");
 }
 
+// tables held by the handle: a population keeps one per member
+size_t table_count(const rl_agent *a) { return a->pop ? a->M : 1; }
+
+// A population's launch shape: grid = members, block and LDS carve as a lone learner
+// group of G lanes gets them (64 lanes per wave, the `lpw` rule's doubling never
+// engages below 1024 lanes).  Host arithmetic only, so rl_population_create runs the
+// LDS guard before its first HIP call.
+int population_select_kernel(rl_agent *a) {
+    a->pop_fn = lookup_population(a->eh.kenv, a->cfg.policy, a->cfg.selector, a->cfg.algo);
+    if (!a->pop_fn) return fail(RL_E_ARG, "no population kernel for this (env, policy, selector, algo)");
+    a->kp.ucb_pack = 0;
+    a->kp.lpw = 64;
+    a->kp.trc_kb = 0;
+    a->block = dim3(((a->G + 63) / 64) * 64);
+    a->grid = dim3(a->M);
+    a->smem = shared_smem_bytes(a->eh.kenv, a->cfg.agent, a->cfg.policy, a->cfg.selector, a->cfg.algo, a->S, a->A,
+                                a->eh.dev_n_start(), a->block.x, 0, a->qrepr == RL_QREPR_F64, 0);
+    if (a->smem > 160 * 1024) return lds_guard_fail(a->smem);
+    a->smem_v[0] = a->smem_v[1] = a->smem;
+    a->trc_kb_v[0] = a->trc_kb_v[1] = 0;
+    return RL_OK;
+}
+
 int agent_select_kernel(rl_agent *a) {
+    if (a->pop) return population_select_kernel(a);
     a->fn = lookup_train(a->eh.kenv, a->cfg.agent, a->cfg.policy, a->cfg.selector, a->cfg.algo,
                          a->priv ? 1 : 0);
     if (!a->fn) return fail(RL_E_ARG, "no kernel for this (env, agent, policy, selector)");
@@ -792,7 +836,7 @@ int agent_reset_policy(rl_agent *a) {
             HIPC(hipStreamSynchronize(a->stream));
         }
     } else {
-        const std::vector<double> v(PSA, a->cfg.q_default);
+        const std::vector<double> v(PSA * table_count(a), a->cfg.q_default);
         return agent_store_table(a, v.data());
     }
     return RL_OK;
@@ -806,21 +850,34 @@ void bj_term_scan(rl_agent *a, const int64_t *q) {
     if (a->cfg.env.kind != RL_ENV_BLACKJACK || a->priv) return;
     const size_t SA = (size_t)a->S * a->A;
     int64_t v[2] = {0, 0};
-    for (uint32_t t = 0; t < a->P; ++t) {
-        bool first = true;
-        for (uint32_t s = 0; s < a->S; ++s) {
-            const uint32_t pl = s >> 6, d = (s >> 1) & 31u;
-            if (pl <= 21u && d <= 10u) continue;
-            for (uint32_t b = 0; b < a->A; ++b) {
-                const size_t i = t * SA + (size_t)s * a->A + b;
-                if (first) { v[t] = q[i]; first = false; }
-                else if (q[i] != v[t]) return;
+    // a population: one word per table over every member's copy (KParams::bj_traw is
+    // one pair for the launch)
+    for (size_t m = 0; m < table_count(a); ++m) {
+        for (uint32_t t = 0; t < a->P; ++t) {
+            bool first = m == 0;
+            for (uint32_t s = 0; s < a->S; ++s) {
+                const uint32_t pl = s >> 6, d = (s >> 1) & 31u;
+                if (pl <= 21u && d <= 10u) continue;
+                for (uint32_t b = 0; b < a->A; ++b) {
+                    const size_t i = (m * a->P + t) * SA + (size_t)s * a->A + b;
+                    if (first) { v[t] = q[i]; first = false; }
+                    else if (q[i] != v[t]) return;
+                }
             }
         }
     }
     a->kp.bj_tconst = 1;
     a->kp.bj_traw[0] = v[0];
     a->kp.bj_traw[1] = v[1];
+}
+
+// the parameter block over member m's lanes only (lane init / arming)
+KParams member_lanes(const rl_agent *a, uint32_t m) {
+    KParams p = a->kp;
+    const size_t o = (size_t)m * a->G;
+    p.L = a->G;
+    p.core = a->core + o; p.rng = a->rng + o; p.aux = a->aux + o; p.epi_reward = a->epi_reward + o;
+    return p;
 }
 
 int agent_reset_selector(rl_agent *a) {
@@ -833,12 +890,17 @@ int agent_reset_selector(rl_agent *a) {
             HIPC(hipStreamSynchronize(a->stream));
         }
     } else {
-        HIPC(hipMemsetAsync(a->n_base, 0, SA * 8, a->stream));
-        const uint64_t one = 1;
-        HIPC(hipMemcpyAsync(a->t_base, &one, 8, hipMemcpyHostToDevice, a->stream));
+        HIPC(hipMemsetAsync(a->n_base, 0, SA * table_count(a) * 8, a->stream));
+        const std::vector<uint64_t> ones(table_count(a), 1);
+        HIPC(hipMemcpyAsync(a->t_base, ones.data(), ones.size() * 8, hipMemcpyHostToDevice, a->stream));
         HIPC(hipStreamSynchronize(a->stream));
     }
-    launch_arm_full(a->kp, -1, 0, 1, a->cfg.eps0, a->stream);
+    if (a->pop) {   // every member's lanes back at the member's own eps0
+        for (uint32_t m = 0; m < a->M; ++m)
+            launch_arm_full(member_lanes(a, m), -1, 0, 1, a->members[m].eps0, a->stream);
+    } else {
+        launch_arm_full(a->kp, -1, 0, 1, a->cfg.eps0, a->stream);
+    }
     HIPC(hipGetLastError());
     HIPC(hipStreamSynchronize(a->stream));
     return RL_OK;
@@ -877,14 +939,13 @@ double env_reward_bound(int kind) {
 // Returns the proven bound on |lr * E * td| (+inf when nothing is proven); the
 // fixed point (|Q| <= 2048) is used only when it is < 2000 (fix_proven), every
 // other table is held in f64 (rl.h rl_q_repr).
-double delta_bound(const rl_agent *a) {
+double delta_bound_cfg(const rl_agent_config &c, bool no_table, double q_abs0) {
     const double inf = std::numeric_limits<double>::infinity();
-    const rl_agent_config &c = a->cfg;
-    if (a->priv || a->neural) return inf;
+    if (no_table) return inf;
     if (c.agent != RL_AGENT_ONE_STEP || c.policy != RL_POLICY_TABULAR) return inf;
     if (c.selector == RL_SEL_UCB && c.algo == RL_ALGO_EXPECTED_SARSA) return inf;
     const double lr = c.lr, g = c.gamma;
-    if (!(lr >= 0.0 && g >= 0.0 && g < 1.0 && std::isfinite(a->q_abs0))) return inf;
+    if (!(lr >= 0.0 && g >= 0.0 && g < 1.0 && std::isfinite(q_abs0))) return inf;
     const double emax = 1.0;   // one-step: the written entry's own error, weight lr
     if (!(lr * emax <= 1.0)) return inf;
     if (c.selector == RL_SEL_EPS_GREEDY && c.algo == RL_ALGO_EXPECTED_SARSA) {
@@ -893,7 +954,7 @@ double delta_bound(const rl_agent *a) {
         if (!(c.eps0 >= 0.0 && c.eps0 <= 1.0 && c.eps_final >= 0.0 && dec)) return inf;
     }
     const double R = env_reward_bound(c.env.kind);
-    const double mb = std::max(a->q_abs0, R / (1.0 - g));
+    const double mb = std::max(q_abs0, R / (1.0 - g));
     if (!(mb <= 2000.0)) return inf;
     // the kernels that rely on this bound also convert episode rewards (at most
     // max_steps + 1 steps of |r| <= R; Blackjack: one +-1) to 2^-16 fixed point
@@ -901,6 +962,16 @@ double delta_bound(const rl_agent *a) {
     const double ep_len = c.env.kind == RL_ENV_BLACKJACK ? 1.0 : (double)c.env.max_steps + 1.0;
     if (!(ep_len * R * 65536.0 < 0x1p50)) return inf;
     return lr * emax * (R + (1.0 + g) * mb);
+}
+double delta_bound(const rl_agent *a) { return delta_bound_cfg(a->cfg, a->priv || a->neural, a->q_abs0); }
+// member m's configuration: the population's with the member's own fields
+rl_agent_config member_config(const rl_agent *a, uint32_t m) {
+    rl_agent_config c = a->cfg;
+    const rl_member_config &mc = a->members[m];
+    c.lr = mc.lr; c.gamma = mc.gamma; c.eps0 = mc.eps0; c.eps_decay = mc.eps_decay; c.eps_final = mc.eps_final;
+    c.ucb_c = mc.ucb_c; c.seed = mc.seed; c.lane_offset = mc.lane_offset;
+    c.n_lanes = a->G;
+    return c;
 }
 // Round 6: on a slippery map the fixed point stays in range
 // but not within the north star's 1e-5 of f64.  Its 2^-40 rounding decides greedy
@@ -913,7 +984,15 @@ bool fix_faithful(const rl_agent *a) {
     const int k = a->cfg.env.kind;
     return !((k == RL_ENV_FROZEN_LAKE || k == RL_ENV_FROZEN_LAKE_EDITED) && a->cfg.env.slippery);
 }
-bool fix_proven(const rl_agent *a) { return delta_bound(a) < 2000.0 && fix_faithful(a); }
+// a population holds one representation: the fixed point only where the proof holds
+// for every member (its own lr / gamma / epsilon schedule)
+bool fix_proven(const rl_agent *a) {
+    if (!fix_faithful(a)) return false;
+    if (!a->pop) return delta_bound(a) < 2000.0;
+    for (uint32_t m = 0; m < a->M; ++m)
+        if (!(delta_bound_cfg(member_config(a, m), false, a->q_abs0) < 2000.0)) return false;
+    return true;
+}
 // The 8-wave kernels pack a step's contributions to an entry into one int64,
 // sum * 2^11 + count (one LDS atomic per contribution instead of two): exact
 // while at most G contributions of at most delta_bound * 2^40 + 1 raw units each
@@ -927,7 +1006,7 @@ bool pack_proven(const rl_agent *a) { return (double)a->G * delta_bound(a) < 200
 // value exact in it), else as f64 bits (NaN canonical).  Same rule as the
 // oracle's o_choose_repr (oracle/rlref.c).
 int agent_store_table(rl_agent *a, const double *vals) {
-    const size_t PSA = (size_t)a->P * a->S * a->A;
+    const size_t PSA = (size_t)a->P * a->S * a->A * table_count(a);
     double amax = 0.0;
     for (size_t i = 0; i < PSA; ++i) {
         const double x = std::fabs(vals[i]);
@@ -946,7 +1025,7 @@ int agent_store_table(rl_agent *a, const double *vals) {
 }
 // the base's values as f64 (either representation)
 int agent_table_values(rl_agent *a, std::vector<double> &vals, std::vector<int64_t> &w) {
-    const size_t PSA = (size_t)a->P * a->S * a->A;
+    const size_t PSA = (size_t)a->P * a->S * a->A * table_count(a);
     w.resize(PSA);
     vals.resize(PSA);
     HIPC(hipMemcpyAsync(w.data(), a->q_base, PSA * 8, hipMemcpyDeviceToHost, a->stream));
@@ -991,6 +1070,15 @@ void merge_layout(const rl_agent *a, uint64_t *max_words, uint64_t *sum_words) {
 
 void agent_sync_params(rl_agent *a) {
     KParams &p = a->kp;
+    if (a->pop) {   // the members' scalars live in the device table (KParams::members); no merge
+        p.decay_kind = a->cfg.decay_kind;
+        p.algo = a->cfg.algo;
+        p.fq = a->qrepr == RL_QREPR_F64 ? 1 : 0;
+        p.pack_ok = 0;
+        p.psal = lds_entries(a);
+        a->pp = PopParams{a->q_base, a->n_base, a->t_base, a->members_d, a->pop_stats_d};
+        return;
+    }
     p.lr = a->cfg.lr;
     p.lr40 = ldexp(a->cfg.lr, 40);
     p.gamma = a->cfg.gamma;
@@ -1028,7 +1116,8 @@ void agent_sync_params(rl_agent *a) {
 // process, its own delta); *merge = true when the fused fold + apply did it
 int launch_train_kernel(rl_agent *a, bool *merge = nullptr) {
     agent_sync_params(a);
-    if (!a->priv) {
+    const bool merges = !a->priv && !a->pop;   // a population's blocks write their tables back themselves
+    if (merges) {
         uint64_t mw, sw;
         merge_layout(a, &mw, &sw);
         if (mw + sw > a->delta_cap)
@@ -1069,7 +1158,8 @@ int launch_train_kernel(rl_agent *a, bool *merge = nullptr) {
         HIPC(hipEventRecord(e0, a->stream));
     }
     {
-        const hipError_t le = a->fn(a->kp, a->grid, a->block, a->smem, a->stream, nullptr);
+        const hipError_t le = a->pop ? a->pop_fn(a->kp, a->pp, a->grid, a->block, a->smem, a->stream, nullptr)
+                                     : a->fn(a->kp, a->grid, a->block, a->smem, a->stream, nullptr);
         if (le != hipSuccess)
             return fail(RL_E_HIP, std::string("train kernel launch (smem ") + std::to_string(a->smem) +
                                       " B, block " + std::to_string(a->block.x) + "): " + hipGetErrorString(le));
@@ -1079,7 +1169,7 @@ int launch_train_kernel(rl_agent *a, bool *merge = nullptr) {
         a->events.emplace_back(e0, e1);
     }
     if (merge) *merge = false;
-    if (!a->priv) {
+    if (merges) {
         if (a->qrepr == RL_QREPR_F64) {   // f64 merge, first phase (UCB: ΔN / Δt from the replicas)
             if (a->cfg.selector == RL_SEL_UCB) launch_fold_replicas(a->kp, a->stream);
             launch_fq_merge_a(a->kp, a->stream);
@@ -1182,7 +1272,7 @@ int launch_and_merge(rl_agent *a) {
     bool merged = false;
     int rc = launch_train_kernel(a, &merged);
     if (rc) return rc;
-    if (merged) return RL_OK;
+    if (merged || a->pop) return RL_OK;   // a population's launch is the train kernel alone
     return merge_after_launch(a);
 }
 // sum of a host value over the ranks (1 rank: itself)
@@ -1790,6 +1880,7 @@ void rl_agent_destroy(rl_agent *a) {
     dfree(a->mcnt); dfree(a->mrec); dfree(a->mslot);
     peer_free(a);
     dfree(a->net_w); dfree(a->feat); dfree(a->ctl_d); dfree(a->call_d);
+    dfree(a->members_d); dfree(a->pop_stats_d);
     if (a->call_h) (void)hipHostFree(a->call_h);
     if (a->env_view) a->env_view->owner = nullptr;   // the view outlives its agent: calls fail with RL_E_STATE
     if (a->ctl_h) (void)hipHostFree(a->ctl_h);
@@ -1800,6 +1891,7 @@ void rl_agent_destroy(rl_agent *a) {
 }
 
 int rl_agent_set_future_q_value_func(rl_agent *a, int32_t algo) {
+    POP_UNSUPPORTED(a, "rl_agent_set_future_q_value_func", nullptr);
     if (!a || algo < 0 || algo > 2) return fail(RL_E_ARG, "bad algo");
     HIPC(hipSetDevice(a->device));
     a->cfg.algo = algo;
@@ -1809,6 +1901,7 @@ int rl_agent_set_future_q_value_func(rl_agent *a, int32_t algo) {
 
 int rl_agent_set_action_selector(rl_agent *a, int32_t sel, double eps0, double eps_decay, double eps_final,
                                  int32_t decay_kind, double ucb_c) {
+    POP_UNSUPPORTED(a, "rl_agent_set_action_selector", nullptr);
     if (!a || sel < 0 || sel > 1 || decay_kind < 0 || decay_kind > 1) return fail(RL_E_ARG, "bad selector");
     HIPC(hipSetDevice(a->device));
     a->cfg.selector = sel;
@@ -1956,6 +2049,7 @@ int rl_agent_lane_state(rl_agent *a, uint32_t *core, uint32_t *aux, size_t n) {
 // across launches like the lane records: each launch reads them in and writes them
 // out once (bench.py's algorithmic bytes for the traces rows)
 int rl_agent_trace_items(rl_agent *a, uint64_t *items) {
+    POP_UNSUPPORTED(a, "rl_agent_trace_items", nullptr);
     if (!a || !items) return fail(RL_E_ARG, "null argument");
     *items = 0;
     if (!a->tcnt) return RL_OK;
@@ -1968,6 +2062,7 @@ int rl_agent_trace_items(rl_agent *a, uint64_t *items) {
 }
 
 int rl_agent_get_q(rl_agent *a, double *out, size_t n) {
+    POP_UNSUPPORTED(a, "rl_agent_get_q", "rl_population_get_q");
     if (!a || !out) return fail(RL_E_ARG, "null argument");
     HIPC(hipSetDevice(a->device));
     const size_t PSA = (size_t)a->P * a->S * a->A;
@@ -2000,6 +2095,7 @@ int rl_agent_get_q(rl_agent *a, double *out, size_t n) {
 }
 
 int rl_agent_set_q(rl_agent *a, const double *in, size_t n) {
+    POP_UNSUPPORTED(a, "rl_agent_set_q", nullptr);
     if (!a || !in) return fail(RL_E_ARG, "null argument");
     if (a->neural) return fail(RL_E_STATE, "NeuralPolicy has no table: use rl_agent_set_weights");
     HIPC(hipSetDevice(a->device));
@@ -2038,6 +2134,7 @@ int rl_agent_set_q_mode(rl_agent *a, int32_t mode) {
 }
 
 int rl_agent_get_q_raw(rl_agent *a, int64_t *out, size_t n) {
+    POP_UNSUPPORTED(a, "rl_agent_get_q_raw", "rl_population_get_q_raw");
     if (!a || !out) return fail(RL_E_ARG, "null argument");
     if (a->priv) return fail(RL_E_STATE, "private mode (group_size 1) keeps f64 Q");
     const size_t PSA = (size_t)a->P * a->S * a->A;
@@ -2049,6 +2146,7 @@ int rl_agent_get_q_raw(rl_agent *a, int64_t *out, size_t n) {
 }
 
 int rl_agent_get_ucb(rl_agent *a, uint64_t *counts, size_t nc, uint64_t *t, size_t nt) {
+    POP_UNSUPPORTED(a, "rl_agent_get_ucb", "rl_population_get_ucb");
     if (!a || !counts || !t) return fail(RL_E_ARG, "null argument");
     HIPC(hipSetDevice(a->device));
     const size_t SA = (size_t)a->S * a->A;
@@ -2067,6 +2165,7 @@ int rl_agent_get_ucb(rl_agent *a, uint64_t *counts, size_t nc, uint64_t *t, size
 }
 
 int rl_agent_set_ucb(rl_agent *a, const uint64_t *counts, size_t nc, const uint64_t *t, size_t nt) {
+    POP_UNSUPPORTED(a, "rl_agent_set_ucb", nullptr);
     if (!a || !counts || !t) return fail(RL_E_ARG, "null argument");
     HIPC(hipSetDevice(a->device));
     const size_t SA = (size_t)a->S * a->A;
@@ -2094,6 +2193,202 @@ int rl_agent_get_epsilon(rl_agent *a, double *out, size_t n) {
     for (size_t i = 0; i < a->L; ++i) {
         const uint64_t b = ((uint64_t)x[i].y << 32) | x[i].x;
         std::memcpy(&out[i], &b, 8);
+    }
+    return RL_OK;
+}
+
+// ---------------------------------------------------------------- population
+// M independent shared-Q agents of G lanes behind one handle and one launch
+// (rl.h).  Every argument is checked before the first HIP call.
+int rl_population_create(const rl_agent_config *base, const rl_member_config *members, uint32_t n_members,
+                         rl_agent **out) {
+    if (!base) return fail(RL_E_ARG, "population: base is null");
+    if (!members) return fail(RL_E_ARG, "population: members is null");
+    if (!out) return fail(RL_E_ARG, "population: out is null");
+    *out = nullptr;
+    const rl_agent_config &c = *base;
+    if (n_members == 0) return fail(RL_E_ARG, "population: n_members must be at least 1");
+    if (c.group_size < 2 || c.group_size > 1024)
+        return fail(RL_E_ARG, "population: group_size (lanes per member) must be within 2..1024, got " +
+                                  std::to_string(c.group_size));
+    const uint64_t lanes = (uint64_t)n_members * c.group_size;
+    if (lanes >= (1ull << 32)) return fail(RL_E_ARG, "population: n_members * group_size must stay below 2^32");
+    if (c.n_lanes != lanes)
+        return fail(RL_E_ARG, "population: n_lanes must be n_members * group_size = " + std::to_string(lanes) +
+                                  ", got " + std::to_string(c.n_lanes));
+    if (c.sync_every == 0) return fail(RL_E_ARG, "population: sync_every must be at least 1");
+    if (c.agent < 0 || c.agent > 1 || c.policy < 0 || c.policy > 2 || c.selector < 0 || c.selector > 1 ||
+        c.algo < 0 || c.algo > 2 || c.decay_kind < 0 || c.decay_kind > 1)
+        return fail(RL_E_ARG, "population: enum out of range");
+    if (c.agent != RL_AGENT_ONE_STEP)
+        return fail(RL_E_ARG, "population: agent must be RL_AGENT_ONE_STEP (eligibility traces are not supported)");
+    if (c.policy == RL_POLICY_NEURAL)
+        return fail(RL_E_ARG, "population: policy must be tabular or double (NeuralPolicy is not supported)");
+    if (c.selector == RL_SEL_UCB && c.algo == RL_ALGO_EXPECTED_SARSA)
+        return fail(RL_E_ARG, "population: selector UCB with algo expected SARSA is not supported");
+    if (c.env.kind < RL_ENV_FROZEN_LAKE || c.env.kind > RL_ENV_BLACKJACK)
+        return fail(RL_E_ARG, "population: env.kind must be FrozenLake, CliffWalking, Taxi or Blackjack "
+                              "(FrozenLakeEdited is not supported)");
+    if (c.env.kind == RL_ENV_FROZEN_LAKE && c.env.map8x8 != 0 && c.env.map8x8 != 1)
+        return fail(RL_E_ARG, "population: env.map8x8 must be a built-in map, 0 or 1 (registered and wide maps "
+                              "are not supported)");
+    rl_agent *a = new rl_agent();
+    a->cfg = c;
+    a->pop = true;
+    a->M = n_members;
+    a->members.assign(members, members + n_members);
+    int rc = build_env(c.env, a->eh);
+    if (rc) { delete a; return rc; }
+    auto bad = [&](int code) { rl_agent_destroy(a); return code; };
+    a->device = c.device;
+    a->S = a->eh.S; a->A = a->eh.A; a->P = c.policy == RL_POLICY_DOUBLE ? 2 : 1;
+    a->L = c.n_lanes; a->G = c.group_size; a->K = c.sync_every;
+    a->n_groups = a->M;
+    // the representation (q_default under every member's proof) and the LDS guard: host arithmetic
+    a->q_abs0 = std::fabs(c.q_default) == std::fabs(c.q_default) ? std::fabs(c.q_default) : INFINITY;
+    a->qrepr = (fix_proven(a) && fix_exact(c.q_default)) ? RL_QREPR_FIXED40 : RL_QREPR_F64;
+    if ((rc = population_select_kernel(a))) { delete a; return rc; }
+
+    if (hipSetDevice(c.device) != hipSuccess) return bad(fail(RL_E_HIP, "hipSetDevice failed (no GPU?)"));
+    if (hipStreamCreateWithFlags(&a->own_stream, hipStreamNonBlocking) != hipSuccess)
+        return bad(fail(RL_E_HIP, "hipStreamCreate failed"));
+    a->stream = a->own_stream;
+    const size_t L = a->L, M = a->M, SA = (size_t)a->S * a->A, PSA = a->P * SA;
+    if ((rc = dalloc(&a->core, L)) || (rc = dalloc(&a->rng, L)) || (rc = dalloc(&a->aux, L)) ||
+        (rc = dalloc(&a->epi_reward, L)) || (rc = dalloc(&a->stats_d, STATS_W * STATS_REP)) ||
+        (rc = dalloc(&a->trans, a->eh.trans.size())) || (rc = dalloc(&a->cdf, a->eh.dev_cdf().size())) ||
+        (rc = dalloc(&a->q_base, M * PSA)) || (rc = dalloc(&a->n_base, M * SA)) || (rc = dalloc(&a->t_base, M)) ||
+        (rc = dalloc(&a->members_d, M)) || (rc = dalloc(&a->pop_stats_d, M * STATS_W)) || (rc = dalloc(&a->ctl_d, 3)))
+        return bad(rc);
+    std::vector<MemberParams> mp(M);
+    for (size_t m = 0; m < M; ++m) {
+        const rl_member_config &mc = a->members[m];
+        const bool mul = c.decay_kind == RL_DECAY_MUL;
+        mp[m] = MemberParams{mc.lr, ldexp(mc.lr, 40), mc.gamma, mul ? mc.eps_decay : 1.0, mul ? 0.0 : mc.eps_decay,
+                             mc.eps_final, mc.ucb_c, 0.0};
+    }
+    if (hipMemcpy(a->members_d, mp.data(), M * sizeof(MemberParams), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(a->pop_stats_d, 0, M * STATS_W * 8) != hipSuccess ||
+        hipMemset(a->stats_d, 0, STATS_W * 8 * STATS_REP) != hipSuccess)
+        return bad(fail(RL_E_HIP, "member table upload"));
+    if (!a->eh.trans.empty() &&
+        hipMemcpy(a->trans, a->eh.trans.data(), a->eh.trans.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+        return bad(fail(RL_E_HIP, "table upload"));
+    if (!a->eh.dev_cdf().empty() &&
+        hipMemcpy(a->cdf, a->eh.dev_cdf().data(), a->eh.dev_cdf().size() * 8, hipMemcpyHostToDevice) != hipSuccess)
+        return bad(fail(RL_E_HIP, "table upload"));
+    if (hipHostMalloc((void **)&a->ctl_h, 6 * 8, hipHostMallocDefault) != hipSuccess ||
+        hipEventCreateWithFlags(&a->ctl_ev[0], hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&a->ctl_ev[1], hipEventDisableTiming) != hipSuccess)
+        return bad(fail(RL_E_HIP, "loop control buffers"));
+
+    KParams &p = a->kp;
+    p.L = a->L; p.G = a->G; p.K = a->K; p.S = a->S; p.A = a->A; p.P = a->P;
+    p.core = a->core; p.rng = a->rng; p.aux = a->aux; p.epi_reward = a->epi_reward;
+    p.q_base = a->q_base; p.n_base = a->n_base; p.t_base = a->t_base;   // member 0's; each block takes its own
+    p.n_rep = 1;
+    p.n_groups = a->M;
+    p.trans = a->trans; p.start_cdf = a->cdf; p.n_start = a->eh.dev_n_start();
+    p.fixed_start = a->eh.fixed_start;
+    p.slippery = a->eh.slippery;
+    p.max_steps = a->eh.max_steps; p.th1 = a->eh.th1; p.th2 = a->eh.th2; p.th3 = a->eh.th3;
+    p.trunc_reward = a->eh.trunc_reward;
+    p.target_episodes = 0; p.eval_at = 0; p.eval_div = 0; p.eval_episodes = c.eval_episodes; p.eval_only = 0;
+    p.stats = a->stats_d;
+    p.rec = nullptr;
+    agent_sync_params(a);
+    for (uint32_t m = 0; m < a->M; ++m) {   // member m's lanes draw from (seed_m, lane_offset_m + i)
+        const rl_member_config &mc = a->members[m];
+        launch_lane_init(c.env.kind, member_lanes(a, m), mc.seed, mc.lane_offset, mc.eps0, a->stream);
+    }
+    if (hipGetLastError() != hipSuccess) return bad(fail(RL_E_HIP, "lane init launch"));
+    if ((rc = agent_reset_policy(a))) return bad(rc);
+    if ((rc = agent_reset_selector(a))) return bad(rc);
+    *out = a;
+    return RL_OK;
+}
+
+namespace {
+int population_window(rl_agent *a, uint32_t m0, uint32_t n, const char *call) {
+    if (!a) return fail(RL_E_ARG, std::string(call) + ": null handle");
+    if (!a->pop) return fail(RL_E_STATE, std::string(call) + ": not a population handle (rl_population_create)");
+    if ((uint64_t)m0 + n > a->M)
+        return fail(RL_E_ARG, std::string(call) + ": members [m0, m0 + n) = [" + std::to_string(m0) + ", " +
+                                  std::to_string((uint64_t)m0 + n) + ") exceed the population's " +
+                                  std::to_string(a->M));
+    return RL_OK;
+}
+}  // namespace
+
+int rl_population_size(rl_agent *a, uint32_t *n_members, uint32_t *lanes_per_member) {
+    if (int rc = population_window(a, 0, 0, "rl_population_size")) return rc;
+    if (n_members) *n_members = a->M;
+    if (lanes_per_member) *lanes_per_member = a->G;
+    return RL_OK;
+}
+
+int rl_population_get_q_raw(rl_agent *a, uint32_t m0, uint32_t n, int64_t *out, size_t n_out) {
+    if (int rc = population_window(a, m0, n, "rl_population_get_q_raw")) return rc;
+    if (!out) return fail(RL_E_ARG, "rl_population_get_q_raw: out is null");
+    const size_t PSA = (size_t)a->P * a->S * a->A;
+    if (n_out != PSA * n)
+        return fail(RL_E_ARG, "rl_population_get_q_raw: n_out must be n * P*S*A = " + std::to_string(PSA * n));
+    if (n == 0) return RL_OK;
+    HIPC(hipSetDevice(a->device));
+    HIPC(hipMemcpyAsync(out, a->q_base + PSA * m0, PSA * n * 8, hipMemcpyDeviceToHost, a->stream));
+    HIPC(hipStreamSynchronize(a->stream));
+    return RL_OK;
+}
+
+int rl_population_get_q(rl_agent *a, uint32_t m0, uint32_t n, double *out, size_t n_out) {
+    if (int rc = population_window(a, m0, n, "rl_population_get_q")) return rc;
+    if (!out) return fail(RL_E_ARG, "rl_population_get_q: out is null");
+    const size_t PSA = (size_t)a->P * a->S * a->A;
+    if (n_out != PSA * n)
+        return fail(RL_E_ARG, "rl_population_get_q: n_out must be n * P*S*A = " + std::to_string(PSA * n));
+    if (n == 0) return RL_OK;
+    std::vector<int64_t> w(PSA * n);
+    if (int rc = rl_population_get_q_raw(a, m0, n, w.data(), w.size())) return rc;
+    for (size_t i = 0; i < w.size(); ++i)
+        out[i] = a->qrepr == RL_QREPR_F64 ? f64_of((uint64_t)w[i]) : q_value(w[i]);
+    return RL_OK;
+}
+
+int rl_population_get_ucb(rl_agent *a, uint32_t m0, uint32_t n, uint64_t *counts, size_t n_counts, uint64_t *t,
+                          size_t n_t) {
+    if (int rc = population_window(a, m0, n, "rl_population_get_ucb")) return rc;
+    if (!counts || !t) return fail(RL_E_ARG, "rl_population_get_ucb: counts / t is null");
+    const size_t SA = (size_t)a->S * a->A;
+    if (n_counts != SA * n)
+        return fail(RL_E_ARG, "rl_population_get_ucb: n_counts must be n * S*A = " + std::to_string(SA * n));
+    if (n_t != n) return fail(RL_E_ARG, "rl_population_get_ucb: n_t must be n = " + std::to_string(n));
+    if (n == 0) return RL_OK;
+    HIPC(hipSetDevice(a->device));
+    HIPC(hipMemcpyAsync(counts, a->n_base + SA * m0, SA * n * 8, hipMemcpyDeviceToHost, a->stream));
+    HIPC(hipMemcpyAsync(t, a->t_base + m0, (size_t)n * 8, hipMemcpyDeviceToHost, a->stream));
+    HIPC(hipStreamSynchronize(a->stream));
+    return RL_OK;
+}
+
+int rl_population_stats(rl_agent *a, uint32_t m0, uint32_t n, rl_stats *out) {
+    if (int rc = population_window(a, m0, n, "rl_population_stats")) return rc;
+    if (!out) return fail(RL_E_ARG, "rl_population_stats: out is null");
+    if (n == 0) return RL_OK;
+    HIPC(hipSetDevice(a->device));
+    std::vector<unsigned long long> s((size_t)n * STATS_W);
+    HIPC(hipMemcpyAsync(s.data(), a->pop_stats_d + (size_t)m0 * STATS_W, s.size() * 8, hipMemcpyDeviceToHost,
+                        a->stream));
+    HIPC(hipStreamSynchronize(a->stream));
+    for (uint32_t m = 0; m < n; ++m) {
+        const unsigned long long *r = &s[(size_t)m * STATS_W];
+        rl_stats &o = out[m];
+        o.train_steps = r[0]; o.eval_steps = r[1]; o.train_episodes = r[2]; o.eval_episodes = r[3];
+        o.reward_sum_q16 = (int64_t)r[4];
+        o.done_lanes = r[5];
+        o.launches = a->launches;
+        o.trace_states = r[7];
+        o.q_clamp_hits = r[ACC_CLAMP];
+        o.delta_saturations = r[ACC_SAT];
     }
     return RL_OK;
 }
@@ -2172,12 +2467,14 @@ int agent_call(rl_agent *a, int op, uint32_t lane0, uint32_t n, const uint64_t *
 }  // namespace
 
 int rl_agent_get_action(rl_agent *a, uint32_t lane, uint64_t obs, uint32_t *action) {
+    POP_UNSUPPORTED(a, "rl_agent_get_action", nullptr);
     if (!a || !action) return fail(RL_E_ARG, "null argument");
     return agent_call(a, CALL_GET_ACTION, lane, 1, &obs, nullptr, nullptr, nullptr, nullptr, nullptr, action,
                       nullptr);
 }
 int rl_agent_update(rl_agent *a, uint32_t lane, uint64_t curr_obs, uint32_t curr_action, double reward,
                     int32_t terminated, uint64_t next_obs, uint32_t next_action, double *td) {
+    POP_UNSUPPORTED(a, "rl_agent_update", nullptr);
     if (!a || !td) return fail(RL_E_ARG, "null argument");
     const uint8_t t = terminated ? 1 : 0;
     return agent_call(a, CALL_UPDATE, lane, 1, &curr_obs, &curr_action, &reward, &t, &next_obs, &next_action,
@@ -2186,6 +2483,7 @@ int rl_agent_update(rl_agent *a, uint32_t lane, uint64_t curr_obs, uint32_t curr
 // every array holds n_lanes entries, and n_lanes must be the agent's lane count
 // (the library read L entries of whatever the caller passed)
 int rl_agent_get_actions(rl_agent *a, const uint64_t *obs, uint32_t *actions, uint64_t n_lanes) {
+    POP_UNSUPPORTED(a, "rl_agent_get_actions", nullptr);
     if (!a || !obs || !actions) return fail(RL_E_ARG, "null argument");
     if (n_lanes != a->L)
         return fail(RL_E_ARG, "n_lanes " + std::to_string(n_lanes) + " != the agent's " + std::to_string(a->L) + " lanes");
@@ -2194,6 +2492,7 @@ int rl_agent_get_actions(rl_agent *a, const uint64_t *obs, uint32_t *actions, ui
 int rl_agent_updates(rl_agent *a, const uint64_t *curr_obs, const uint32_t *curr_action, const double *reward,
                      const uint8_t *terminated, const uint64_t *next_obs, const uint32_t *next_action, double *td,
                      uint64_t n_lanes) {
+    POP_UNSUPPORTED(a, "rl_agent_updates", nullptr);
     if (!a || !curr_obs || !curr_action || !reward || !terminated || !next_obs || !next_action || !td)
         return fail(RL_E_ARG, "null argument");
     if (n_lanes != a->L)
@@ -2203,6 +2502,7 @@ int rl_agent_updates(rl_agent *a, const uint64_t *curr_obs, const uint32_t *curr
 }
 
 int rl_agent_env(rl_agent *a, rl_env **out) {
+    POP_UNSUPPORTED(a, "rl_agent_env", nullptr);
     if (!a || !out) return fail(RL_E_ARG, "null argument");
     *out = nullptr;
     if (a->env_view) return fail(RL_E_STATE, "this agent already has an Env view (rl_env_destroy it first)");
@@ -2236,6 +2536,7 @@ int rl_agent_env(rl_agent *a, rl_env **out) {
 }
 
 int rl_agent_set_recording(rl_agent *a, int32_t enable) {
+    POP_UNSUPPORTED(a, "rl_agent_set_recording", nullptr);
     if (!a) return fail(RL_E_ARG, "null agent");
     HIPC(hipSetDevice(a->device));
     if (enable && !a->rec_d) {
@@ -2247,6 +2548,7 @@ int rl_agent_set_recording(rl_agent *a, int32_t enable) {
 }
 
 int rl_agent_take_records(rl_agent *a, rl_step_record *out, uint64_t cap, uint64_t *n_total) {
+    POP_UNSUPPORTED(a, "rl_agent_take_records", nullptr);
     if (!a) return fail(RL_E_ARG, "null agent");
     if (n_total) *n_total = a->rec_h.size();
     if (out) {
@@ -2258,12 +2560,14 @@ int rl_agent_take_records(rl_agent *a, rl_step_record *out, uint64_t cap, uint64
 }
 
 int rl_agent_set_reset_step(rl_agent *a, int32_t enable) {
+    POP_UNSUPPORTED(a, "rl_agent_set_reset_step", nullptr);
     if (!a) return fail(RL_E_ARG, "null agent");
     a->kp.reset_step = enable ? 1 : 0;
     return RL_OK;
 }
 
 int rl_agent_set_planning(rl_agent *a, uint32_t planning_steps) {
+    POP_UNSUPPORTED(a, "rl_agent_set_planning", nullptr);
     if (!a) return fail(RL_E_ARG, "null agent");
     if (planning_steps && !a->priv) return fail(RL_E_ARG, "Dyna planning needs group_size 1 (private agents)");
     HIPC(hipSetDevice(a->device));
@@ -2286,6 +2590,7 @@ int rl_agent_set_planning(rl_agent *a, uint32_t planning_steps) {
 }
 
 int rl_agent_set_episode_log(rl_agent *a, uint32_t capacity_per_lane) {
+    POP_UNSUPPORTED(a, "rl_agent_set_episode_log", nullptr);
     if (!a) return fail(RL_E_ARG, "null agent");
     HIPC(hipSetDevice(a->device));
     HIPC(hipStreamSynchronize(a->stream));
@@ -2307,6 +2612,7 @@ int rl_agent_set_episode_log(rl_agent *a, uint32_t capacity_per_lane) {
 
 int rl_agent_take_episodes(rl_agent *a, rl_episode_record *out, uint64_t cap, uint64_t *n_total,
                            uint64_t *n_lost) {
+    POP_UNSUPPORTED(a, "rl_agent_take_episodes", nullptr);
     if (!a) return fail(RL_E_ARG, "null agent");
     if (!a->elog_cap) return fail(RL_E_STATE, "episode log not enabled");
     HIPC(hipSetDevice(a->device));
@@ -2333,6 +2639,7 @@ int rl_agent_take_episodes(rl_agent *a, rl_episode_record *out, uint64_t cap, ui
 }
 
 int rl_agent_delta_words(rl_agent *a, uint64_t *n) {
+    POP_UNSUPPORTED(a, "rl_agent_delta_words", nullptr);
     if (!a || !n) return fail(RL_E_ARG, "null argument");
     uint64_t mw = 0, sw = 0;
     if (!a->priv) merge_layout(a, &mw, &sw);
@@ -2340,6 +2647,7 @@ int rl_agent_delta_words(rl_agent *a, uint64_t *n) {
     return RL_OK;
 }
 int rl_agent_delta_max_words(rl_agent *a, uint64_t *n) {
+    POP_UNSUPPORTED(a, "rl_agent_delta_max_words", nullptr);
     if (!a || !n) return fail(RL_E_ARG, "null argument");
     uint64_t mw = 0, sw = 0;
     if (!a->priv) merge_layout(a, &mw, &sw);
@@ -2350,6 +2658,7 @@ int rl_agent_delta_max_words(rl_agent *a, uint64_t *n) {
 // buffer of this size survives every representation switch (set_action_selector,
 // set_future_q_value_func, set_q_mode, set_q)
 int rl_agent_delta_cap_words(rl_agent *a, uint64_t *n) {
+    POP_UNSUPPORTED(a, "rl_agent_delta_cap_words", nullptr);
     if (!a || !n) return fail(RL_E_ARG, "null argument");
     *n = 0;
     if (a->priv) return RL_OK;
@@ -2361,6 +2670,7 @@ int rl_agent_delta_cap_words(rl_agent *a, uint64_t *n) {
 }
 
 int rl_agent_set_delta_buffer(rl_agent *a, void *ptr, uint64_t n_words) {
+    POP_UNSUPPORTED(a, "rl_agent_set_delta_buffer", nullptr);
     if (!a) return fail(RL_E_ARG, "null agent");
     if (a->priv) return fail(RL_E_STATE, "private mode has no merge");
     uint64_t mw, sw;
@@ -2373,6 +2683,7 @@ int rl_agent_set_delta_buffer(rl_agent *a, void *ptr, uint64_t n_words) {
 }
 
 int rl_agent_set_merge_groups(rl_agent *a, uint64_t total_groups) {
+    POP_UNSUPPORTED(a, "rl_agent_set_merge_groups", nullptr);
     if (!a) return fail(RL_E_ARG, "null agent");
     a->merge_groups = total_groups ? total_groups : a->n_groups;
     a->merge_groups_set = true;
@@ -2380,12 +2691,14 @@ int rl_agent_set_merge_groups(rl_agent *a, uint64_t total_groups) {
 }
 
 int rl_agent_launch_train(rl_agent *a) {
+    POP_UNSUPPORTED(a, "rl_agent_launch_train", nullptr);
     if (!a) return fail(RL_E_ARG, "null agent");
     HIPC(hipSetDevice(a->device));
     return launch_train_kernel(a);
 }
 
 int rl_agent_launch_fold(rl_agent *a) {
+    POP_UNSUPPORTED(a, "rl_agent_launch_fold", nullptr);
     if (!a) return fail(RL_E_ARG, "null agent");
     HIPC(hipSetDevice(a->device));
     // an external collective must declare the learner groups of every rank: the
@@ -2397,6 +2710,7 @@ int rl_agent_launch_fold(rl_agent *a) {
 }
 
 int rl_agent_launch_apply(rl_agent *a) {
+    POP_UNSUPPORTED(a, "rl_agent_launch_apply", nullptr);
     if (!a) return fail(RL_E_ARG, "null agent");
     HIPC(hipSetDevice(a->device));
     return launch_apply_kernel(a);
@@ -2515,6 +2829,7 @@ int comm_peer_setup(rl_agent *a) {
 }  // namespace
 
 int rl_agent_set_comm(rl_agent *a, rl_comm *c) {
+    POP_UNSUPPORTED(a, "rl_agent_set_comm", nullptr);
     if (!a) return fail(RL_E_ARG, "null agent");
     if (c && a->priv) return fail(RL_E_STATE, "private mode (group_size 1) has no merge to reduce");
     if (c && c->device != a->device) return fail(RL_E_ARG, "communicator and agent on different devices");
@@ -2539,6 +2854,7 @@ int rl_agent_set_comm(rl_agent *a, rl_comm *c) {
 }
 
 int rl_agent_sync(rl_agent *a) {
+    POP_UNSUPPORTED(a, "rl_agent_sync", nullptr);
     if (!a) return fail(RL_E_ARG, "null agent");
     if (a->priv) return RL_OK;
     HIPC(hipSetDevice(a->device));
@@ -2631,6 +2947,7 @@ int peer_selftest(rl_agent *a, bool *ok) {
 }  // namespace
 
 int rl_agent_peer_handle(rl_agent *a, void *handle_out) {
+    POP_UNSUPPORTED(a, "rl_agent_peer_handle", nullptr);
     if (!a || !handle_out) return fail(RL_E_ARG, "null argument");
     if (a->priv) return fail(RL_E_STATE, "private mode (group_size 1) has no merge to reduce");
     HIPC(hipSetDevice(a->device));
@@ -2643,6 +2960,7 @@ int rl_agent_peer_handle(rl_agent *a, void *handle_out) {
 }
 
 int rl_agent_peer_attach(rl_agent *a, int32_t rank, int32_t world, const void *handles) {
+    POP_UNSUPPORTED(a, "rl_agent_peer_attach", nullptr);
     if (!a || !handles || world < 1 || rank < 0 || rank >= world) return fail(RL_E_ARG, "bad rank / world / handles");
     if (a->priv) return fail(RL_E_STATE, "private mode (group_size 1) has no merge to reduce");
     HIPC(hipSetDevice(a->device));
@@ -2678,6 +2996,7 @@ int rl_agent_peer_attach(rl_agent *a, int32_t rank, int32_t world, const void *h
 }
 
 int rl_agent_merge_path(rl_agent *a, int32_t *path) {
+    POP_UNSUPPORTED(a, "rl_agent_merge_path", nullptr);
     if (!a || !path) return fail(RL_E_ARG, "null argument");
     *path = a->peer.on ? RL_MERGE_PEER : (a->comm ? RL_MERGE_RCCL : RL_MERGE_LOCAL);
     return RL_OK;
@@ -2694,7 +3013,8 @@ int rl_agent_occupancy(rl_agent *a, uint32_t *groups_per_cu, uint64_t *lds_bytes
     HIPC(hipSetDevice(a->device));
     agent_sync_params(a);   // the kernel choice depends on the Q representation (KParams::fq)
     int n = 0;
-    HIPC(a->fn(a->kp, a->grid, a->block, a->smem, a->stream, &n));
+    if (a->pop) HIPC(a->pop_fn(a->kp, a->pp, a->grid, a->block, a->smem, a->stream, &n));
+    else HIPC(a->fn(a->kp, a->grid, a->block, a->smem, a->stream, &n));
     *groups_per_cu = (uint32_t)n;
     *lds_bytes = a->smem;
     *block_threads = a->block.x;
@@ -2779,6 +3099,7 @@ int rl_kat_ucb(int32_t device, const double *q, const double *nc, const uint64_t
 extern "C" {
 
 int rl_agent_net_dims(rl_agent *a, uint32_t *n_in, uint32_t *hidden, uint32_t *n_params) {
+    POP_UNSUPPORTED(a, "rl_agent_net_dims", nullptr);
     if (!a || !n_in || !hidden || !n_params) return fail(RL_E_ARG, "null argument");
     if (!a->neural) return fail(RL_E_STATE, "not a NeuralPolicy agent");
     *n_in = a->n_in;
@@ -2788,6 +3109,7 @@ int rl_agent_net_dims(rl_agent *a, uint32_t *n_in, uint32_t *hidden, uint32_t *n
 }
 
 int rl_agent_get_weights(rl_agent *a, double *out, size_t n) {
+    POP_UNSUPPORTED(a, "rl_agent_get_weights", nullptr);
     if (!a || !out) return fail(RL_E_ARG, "null argument");
     if (!a->neural) return fail(RL_E_STATE, "not a NeuralPolicy agent");
     const size_t np = a->n_params, L = a->L;
@@ -2805,6 +3127,7 @@ int rl_agent_get_weights(rl_agent *a, double *out, size_t n) {
 // rl_agent_get_q's / rl_agent_get_weights' layouts, without the whole set's copy
 // (2^20 lanes of cfg 7 hold 1.6 GB of Q): the bench's q_check and the full-size tests
 int rl_agent_get_q_lanes(rl_agent *a, uint32_t lane0, uint32_t n_lanes, double *out, size_t n) {
+    POP_UNSUPPORTED(a, "rl_agent_get_q_lanes", nullptr);
     if (!a || !out) return fail(RL_E_ARG, "null argument");
     if (!a->priv) return fail(RL_E_STATE, "shared mode: one merged table (rl_agent_get_q)");
     if ((uint64_t)lane0 + n_lanes > a->L) return fail(RL_E_ARG, "lane window out of range");
@@ -2828,6 +3151,7 @@ int rl_agent_get_q_lanes(rl_agent *a, uint32_t lane0, uint32_t n_lanes, double *
     return RL_OK;
 }
 int rl_agent_get_weights_lanes(rl_agent *a, uint32_t lane0, uint32_t n_lanes, double *out, size_t n) {
+    POP_UNSUPPORTED(a, "rl_agent_get_weights_lanes", nullptr);
     if (!a || !out) return fail(RL_E_ARG, "null argument");
     if (!a->neural) return fail(RL_E_STATE, "not a NeuralPolicy agent");
     if ((uint64_t)lane0 + n_lanes > a->L) return fail(RL_E_ARG, "lane window out of range");
@@ -2844,6 +3168,7 @@ int rl_agent_get_weights_lanes(rl_agent *a, uint32_t lane0, uint32_t n_lanes, do
 }
 
 int rl_agent_set_weights(rl_agent *a, const double *in, size_t n) {
+    POP_UNSUPPORTED(a, "rl_agent_set_weights", nullptr);
     if (!a || !in) return fail(RL_E_ARG, "null argument");
     if (!a->neural) return fail(RL_E_STATE, "not a NeuralPolicy agent");
     const size_t np = a->n_params, L = a->L;

@@ -75,6 +75,14 @@ struct AgentCall {
     double *td_out;
 };
 
+// A population (rl.h rl_population_create): M independent shared-Q agents of G lanes
+// in one launch, workgroup m = member m.  The member's hyper-parameters as the step
+// loop reads them (KParams::lr .. ucb_c); 64 bytes, read once per block with scalar
+// loads (the index is the block's)
+struct MemberParams {
+    double lr, lr40, gamma, eps_dm, eps_ds, eps_final, ucb_c, pad;
+};
+
 struct KParams {
     uint32_t L, G, K, S, A, P;
     // per-call Agent surface (private mode): CALL_NONE for the training launches
@@ -193,6 +201,20 @@ struct KParams {
     uint32_t net_regs;     // 1: NeuralPolicy lanes of the bin's network run k_train_private_net (rl_train_impl.h)
 };
 
+// The population kernels' second argument (k_train_population, rl_train_population.hip):
+// every member's tables, counters and scalars, and its own stats row; block m takes
+// row m of each.  Kept out of KParams so that the other kernels' argument block, and
+// with it their code, stays what it was.
+struct PopParams {
+    int64_t *q;                // [M][P][S][A] words of the population's representation
+    uint64_t *n;               // [M][S][A]
+    uint64_t *t;               // [M]
+    const MemberParams *members;   // [M]
+    unsigned long long *stats; // [M][STATS_W], rl_stats slots as KParams::stats (5: the last launch's)
+};
+typedef hipError_t (*pop_launch_fn)(const KParams &p, const PopParams &pp, dim3 grid, dim3 block, size_t smem,
+                                    hipStream_t stream, int *occ);
+
 // one entry per (env, agent, policy, selector, private) kernel instantiation
 // occ != nullptr: no launch; *occ = resident workgroups per CU of the kernel
 // the launch would pick (hipOccupancyMaxActiveBlocksPerMultiprocessor)
@@ -207,6 +229,9 @@ inline bool layout_sparse_traces(int agent, int sel, int algo, int priv) {
     return agent == RL_AGENT_TRACES && !priv && !(sel == RL_SEL_UCB && algo == RL_ALGO_EXPECTED_SARSA);
 }
 train_launch_fn lookup_train(int env, int agent, int policy, int sel, int algo, int priv);
+// the population kernel of a one-step (env, policy, selector, algorithm); nullptr outside
+// the supported slice (rl_train_population.hip)
+pop_launch_fn lookup_population(int env, int policy, int sel, int algo);
 size_t shared_smem_bytes(int env, int agent, int policy, int sel, int algo, uint32_t S, uint32_t A,
                          uint32_t n_start, uint32_t nthr, uint32_t trc_kb, int fq, int ucb_pack);
 size_t private_smem_bytes(int env, int agent, int policy, int sel, uint32_t S, uint32_t A, uint32_t n_start);

@@ -508,9 +508,13 @@ constexpr bool fix_possible() {
 // enabled); the throughput variant carries neither.
 // FQ: the group's Q is f64 (rl_device.h "f64 shared Q"); else the fixed point,
 // which the host runs only where it proved the range (no clamp can engage).
+// POP: the block is member blockIdx.x of a population (rl_train_population.hip): p
+// holds that member's bases and scalars and pop_row is its stats row; the block is
+// the only writer of its tables, so it writes them back itself instead of emitting a
+// merge delta.
 template <int ENV, int AGENT, int POLICY, int SEL, int ALGO, bool INSTR, bool FQ, int SLIP = -1, int SWEEP = -1,
-          bool PACK = false, int RS = -1, int EPI = -1>
-__device__ __forceinline__ void train_shared_body(const KParams &p) {
+          bool PACK = false, int RS = -1, int EPI = -1, bool POP = false>
+__device__ __forceinline__ void train_shared_body(const KParams &p, unsigned long long *pop_row = nullptr) {
     using E = EnvDev<ENV>;
     constexpr int A = E::A;
     constexpr int P = POLICY == RL_POLICY_DOUBLE ? 2 : 1;
@@ -1703,6 +1707,33 @@ __device__ __forceinline__ void train_shared_body(const KParams &p) {
     // ΔQ and group counts into replica blockIdx % n_rep of the SUM words ([PSA
     // sums][PSA group counts][SA dN][1 dt], folded by k_fold_replicas); f64: the
     // group's Q values into its slot (k_fq_merge_a / _b take the mean).
+    if constexpr (POP) {
+        // ---------------- population: no merge.  The tables go straight back to the
+        // member's base (p.q_base / n_base / t_base are the member's rows), as the merge
+        // over this one group would leave them: the fixed point moves by the group's
+        // own delta (mean over one group); an f64 entry the group changed takes its
+        // value on the value's own grid, which is the value itself except that -0.0
+        // has raw 0 there and becomes +0.0 (k_fq_merge_b / k_fq_apply); NaN is
+        // already canonical in LDS (settle_fq).  Blackjack's compact rows map back
+        // through dense_of, so its terminal rows are never written.
+        __syncthreads();
+        // the member's own stats row: one block owns it, so plain adds (5: this launch's)
+        if (tid < STATS_W && tid != 6) pop_row[tid] = tid == 5 ? ACC[5] : pop_row[tid] + ACC[tid];
+        for (uint32_t j = tid; j < PSAL; j += nthr) {
+            const uint32_t i = dense_of(j);
+            unsigned long long w = Q[j];
+            if (w != (unsigned long long)p.q_base[i]) {
+                if constexpr (FQ) w = w == 0x8000000000000000ull ? 0ull : w;
+                p.q_base[i] = (int64_t)w;
+            }
+        }
+        if constexpr (UCB) {
+            static_assert(!POP || !SPEC, "population: UCB + expected SARSA keeps its counters in the merge");
+            for (uint32_t i = tid; i < SA; i += nthr) p.n_base[i] = N[lds_of(i)];
+            if (tid == 0) p.t_base[0] = T[0];
+        }
+        return;
+    }
     int64_t *const dl = p.delta_rep + (uint64_t)(blockIdx.x % p.n_rep) * p.delta_words;
     __syncthreads();
     if constexpr (FQ) {

@@ -57,6 +57,13 @@ class AgentConfig(C.Structure):
     ]
 
 
+class MemberConfig(C.Structure):
+    """rl.h rl_member_config: what one member of a Population has of its own"""
+    _fields_ = [("lr", C.c_double), ("gamma", C.c_double), ("eps0", C.c_double),
+                ("eps_decay", C.c_double), ("eps_final", C.c_double), ("ucb_c", C.c_double),
+                ("seed", C.c_uint64), ("lane_offset", C.c_uint64)]
+
+
 class Stats(C.Structure):
     _fields_ = [("train_steps", C.c_uint64), ("eval_steps", C.c_uint64),
                 ("train_episodes", C.c_uint64), ("eval_episodes", C.c_uint64),
@@ -168,6 +175,12 @@ SIGNATURES = {
     "rl_agent_get_q_lanes": (C.c_int, [_V, C.c_uint32, C.c_uint32, _V, C.c_size_t]),
     "rl_agent_get_weights_lanes": (C.c_int, [_V, C.c_uint32, C.c_uint32, _V, C.c_size_t]),
     "rl_agent_trace_items": (C.c_int, [_V, _P(C.c_uint64)]),
+    "rl_population_create": (C.c_int, [_P(AgentConfig), _P(MemberConfig), C.c_uint32, _P(_V)]),
+    "rl_population_size": (C.c_int, [_V, _P(C.c_uint32), _P(C.c_uint32)]),
+    "rl_population_get_q": (C.c_int, [_V, C.c_uint32, C.c_uint32, _V, C.c_size_t]),
+    "rl_population_get_q_raw": (C.c_int, [_V, C.c_uint32, C.c_uint32, _V, C.c_size_t]),
+    "rl_population_get_ucb": (C.c_int, [_V, C.c_uint32, C.c_uint32, _V, C.c_size_t, _V, C.c_size_t]),
+    "rl_population_stats": (C.c_int, [_V, C.c_uint32, C.c_uint32, _P(Stats)]),
 }
 PEER_HANDLE_BYTES = 64
 MERGE_PATHS = {0: "local", 1: "rccl", 2: "peer"}
@@ -668,6 +681,157 @@ class Agent:
 
     def set_stream(self, stream_ptr):
         check(lib().rl_agent_set_stream(self.h, C.c_void_p(stream_ptr)))
+
+    def occupancy(self):
+        g, b, t = C.c_uint32(), C.c_uint64(), C.c_uint32()
+        check(lib().rl_agent_occupancy(self.h, C.byref(g), C.byref(b), C.byref(t)))
+        return {"groups_per_cu": g.value, "lds_bytes": b.value, "block_threads": t.value}
+
+    def set_timing(self, on=True):
+        check(lib().rl_agent_set_timing(self.h, int(on)))
+
+    def timing(self):
+        ms, n = C.c_double(), C.c_uint64()
+        check(lib().rl_agent_get_timing(self.h, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+
+MEMBER_KEYS = ("lr", "gamma", "eps0", "eps_decay", "eps_final", "ucb_c", "seed", "lane_offset")
+
+
+def member_params(base, member):
+    """the parameters of one member: the base's with the member's overrides, and
+    default_params' eps_decay rule (eps0 / (exploration_time * n_episodes_for_decay))
+    for a member that changes eps0 without naming eps_decay"""
+    unknown = set(member) - set(MEMBER_KEYS)
+    if unknown:
+        raise ValueError(f"not per-member fields: {sorted(unknown)}")
+    p = dict(base)
+    p.update(member)
+    if "eps_decay" not in member and "eps0" in member:
+        p["eps_decay"] = p["eps0"] / (p["exploration_time"] * p["n_episodes_for_decay"])
+    return p
+
+
+def member_configs(base, members):
+    arr = (MemberConfig * max(len(members), 1))()
+    for i, m in enumerate(members):
+        p = member_params(base, m)
+        for k in MEMBER_KEYS[:6]:
+            setattr(arr[i], k, float(p[k]))
+        arr[i].seed, arr[i].lane_offset = p["seed"], p["lane_offset"]
+    return arr
+
+
+class Population:
+    """M independent shared-Q agents in one launch (rl.h rl_population_create): member
+    m is the Agent of member_params(base, members[m]) with n_lanes = group_size = G.
+    base_params: default_params(...) with group_size = G (n_lanes is set to M * G);
+    members: dicts overriding MEMBER_KEYS."""
+
+    def __init__(self, base_params, members):
+        members = list(members)
+        self.M, self.G = len(members), base_params["group_size"]
+        self.p = dict(base_params, n_lanes=self.M * self.G)
+        self.members = [member_params(self.p, m) for m in members]
+        self.cfg = agent_config(self.p)
+        self._mc = member_configs(self.p, members)
+        h = C.c_void_p()
+        check(lib().rl_population_create(C.byref(self.cfg), self._mc, self.M, C.byref(h)))
+        self.h = h
+        S, A, P = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        check(lib().rl_agent_dims(self.h, C.byref(S), C.byref(A), C.byref(P)))
+        self.S, self.A, self.P = S.value, A.value, P.value
+        self.L = self.M * self.G
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().rl_agent_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def size(self):
+        m, g = C.c_uint32(), C.c_uint32()
+        check(lib().rl_population_size(self.h, C.byref(m), C.byref(g)))
+        return m.value, g.value
+
+    def _window(self, m0, n):
+        return m0, (self.M - m0 if n is None else n)
+
+    def run(self, n_launches):
+        check(lib().rl_agent_run(self.h, n_launches))
+
+    def synchronize(self):
+        check(lib().rl_agent_synchronize(self.h))
+
+    def train(self, n_episodes, eval_at=0):
+        st = Stats()
+        check(lib().rl_agent_train(self.h, n_episodes, eval_at, C.byref(st)))
+        return st.as_dict()
+
+    def evaluate(self, n_episodes):
+        st = Stats()
+        check(lib().rl_agent_evaluate(self.h, n_episodes, C.byref(st)))
+        return st.as_dict()
+
+    def reset(self):
+        check(lib().rl_agent_reset(self.h))
+
+    def stats(self):
+        """totals over the members"""
+        st = Stats()
+        check(lib().rl_agent_stats(self.h, C.byref(st)))
+        return st.as_dict()
+
+    def member_stats(self, m0=0, n=None):
+        m0, n = self._window(m0, n)
+        arr = (Stats * max(n, 1))()
+        check(lib().rl_population_stats(self.h, m0, n, arr))
+        return [arr[i].as_dict() for i in range(n)]
+
+    def q(self, m0=0, n=None):
+        m0, n = self._window(m0, n)
+        out = np.zeros((n, self.P, self.S, self.A), np.float64)
+        check(lib().rl_population_get_q(self.h, m0, n, out.ctypes.data, out.size))
+        return out
+
+    def q_raw(self, m0=0, n=None):
+        """[member][P][S][A] raw words: fixed-point integers or f64 bits (q_repr())"""
+        m0, n = self._window(m0, n)
+        out = np.zeros((n, self.P, self.S, self.A), np.int64)
+        check(lib().rl_population_get_q_raw(self.h, m0, n, out.ctypes.data, out.size))
+        return out
+
+    def ucb(self, m0=0, n=None):
+        """([member][S][A] counts, [member] t)"""
+        m0, n = self._window(m0, n)
+        cnt = np.zeros((n, self.S, self.A), np.uint64)
+        t = np.zeros(n, np.uint64)
+        check(lib().rl_population_get_ucb(self.h, m0, n, cnt.ctypes.data, cnt.size, t.ctypes.data, t.size))
+        return cnt, t
+
+    def epsilon(self):
+        """[member][lane] epsilons"""
+        out = np.zeros(self.L, np.float64)
+        check(lib().rl_agent_get_epsilon(self.h, out.ctypes.data, self.L))
+        return out.reshape(self.M, self.G)
+
+    def lane_state(self):
+        """([member][lane][4] core, [member][lane][4] aux) records (rl_agent_lane_state)"""
+        core = np.zeros((self.L, 4), np.uint32)
+        aux = np.zeros((self.L, 4), np.uint32)
+        check(lib().rl_agent_lane_state(self.h, core.ctypes.data, aux.ctypes.data, self.L))
+        return core.reshape(self.M, self.G, 4), aux.reshape(self.M, self.G, 4)
+
+    def q_repr(self):
+        r = C.c_int32()
+        check(lib().rl_agent_q_repr(self.h, C.byref(r)))
+        return QREPR[r.value]
+
+    def set_q_mode(self, mode):
+        check(lib().rl_agent_set_q_mode(self.h, QMODE[mode]))
 
     def occupancy(self):
         g, b, t = C.c_uint32(), C.c_uint64(), C.c_uint32()
