@@ -504,6 +504,8 @@ class Batch:
         lib().rlo_batch_lane_eps(self.h, out.ctypes.data)
         return out
 
+    epsilon = lane_eps          # the device Agent's name for it
+
     def weights(self):
         _, n_par = net_dims(self.p)
         out = np.zeros(self.L * n_par, np.float64)

@@ -1,20 +1,23 @@
 """An exact replay model of one shared-mode launch (group_size >= 2).
 
 TEST INFRASTRUCTURE ONLY.  This is a third statement of the shared-Q contract,
-written from DESIGN.md section 2 ("Step combine", "Merge", "Fixed point", "UCB")
-and the include/rl.h comment on rl_q_repr.  It uses neither the CPU oracle nor
-the library: no ctypes, no RNG, no env.  Everything it needs is in the data
-both sides already expose:
+written from DESIGN.md section 2 ("Step combine", "Traces", "Merge", "Fixed
+point", "UCB"), the include/rl.h comment on rl_q_repr and the reference's
+sources it cites.  It uses neither the CPU oracle nor the library: no ctypes, no
+RNG, no env.  Everything it needs is in the data both sides already expose:
 
   - the raw words of Q_base and the UCB counters N / t before the launch;
   - the launch's rl_step_record entries as records[K][n_lanes]
-    (fields s, a, r, s2, a2, term, mode, kind, td).
+    (fields s, a, r, s2, a2, term, mode, kind, td);
+  - the per-lane epsilon before the first launch (epsilon()), carried by the
+    model from then on;
+  - ln(t) of the side under test as a callable (see "ln" below).
 
-From those it predicts the raw words of Q_base and N / t after the launch, bit
-for bit.  Arithmetic is Python int and fractions.Fraction where the contract
-says "exact", and CPython floats (IEEE binary64, correctly rounded float(int),
-a * b, a + b, no fused multiply-add) where the contract names a rounded
-operation.
+From those it predicts the raw words of Q_base, N / t and every lane's epsilon
+after the launch, bit for bit.  Arithmetic is Python int and fractions.Fraction
+where the contract says "exact", and CPython floats (IEEE binary64, correctly
+rounded float(int), a * b, a + b, a / b, sqrt, no fused multiply-add) where the
+contract names a rounded operation.
 
 What the model restates
 -----------------------
@@ -26,16 +29,25 @@ starting from Q_base, for each of the K synchronous steps:
     the reference's operation order (src/agent.rs:19-45,
     src/agent/one_step_agent.rs:62-72):
         td = (r + gamma * next) - V[s][a]
-    with next = V[s2][a2] (SARSA) or the first maximum of V[s2][:] found with a
-    strict `>` from element 0 (Q-learning, src/utils.rs:13-21).  V is the value
-    table; for the double policy V and the updated table alternate per update
-    (double_tabular_policy.rs:41-67: flag true reads alpha = table 0 and writes
-    beta = table 1).  The recomputed td must equal the recorded one bit for bit
-    (NaN as NaN); differences are returned in Replay.td_mismatches.
-    For expected SARSA the recorded td is the INPUT: its probabilities need the
-    per-lane epsilon and the group's UCB state, which the oracle parity tests
-    cover and this model does not.
-  * the contribution is d = lr * td to entry (update table, s, a).
+    with next = V[s2][a2] (SARSA), the first maximum of V[s2][:] found with a
+    strict `>` from element 0 (Q-learning, src/utils.rs:13-21), or expected
+    SARSA's f = 0.0; f += p[i] * V[s2][i] in index order with
+      - eps-greedy (uniform_epsilon_greed.rs:72-76): p[i] = eps / A, then
+        p[argmax V[s2]] = 1 - eps, eps the LANE's epsilon at this update, before
+        the decay the update may trigger (:42-49, on `term`);
+      - UCB (upper_confidence_bound.rs:48-63): u_i = V[s2][i] + c * sqrt(ln(t) /
+        (n_i + 2^-1022)), sum accumulated from 0.0 in order, p_i = u_i / sum,
+        with n and t the GROUP's counters: N_base / t_base plus the group's own
+        increments up to and including this step's selections.
+    Division and square root are IEEE (x / 0, inf / inf, sqrt(nan) give inf /
+    NaN, not an exception), so the NaN regime from fresh counters is
+    replayed, not refused.  V is the value table; for the double policy V and
+    the updated table alternate per update (double_tabular_policy.rs:41-67:
+    flag true reads alpha = table 0 and writes beta = table 1).  The recomputed
+    td must equal the recorded one bit for bit (NaN as NaN); differences are
+    returned in Replay.td_mismatches.  td_source="record" takes the recorded td
+    as the input instead (the hand-worked combine tests inject tds this way).
+  * one-step agent: the contribution is d = lr * td to entry (update table, s, a).
   * f64: the n contributions an entry received in the step move it by their
     mean, summed exactly on the grid of the largest: with `code` the largest
     biased exponent among them, e = max(code, 1) - 1075, every d is rounded
@@ -48,6 +60,22 @@ starting from Q_base, for each of the K synchronous steps:
     the host proved |Q| <= 2048 and every contribution finite; a non-finite or
     out-of-range value is outside the written contract and the model raises.
 
+Eligibility traces (f64 only; elegibility_traces_agent.rs:61-104)
+------------------------------------------------------------------
+Each lane keeps a sparse E[s][a] over the states it visited this episode (the
+reference's FxHashMap of rows), carried across launches like the flags, empty at
+creation, after reset() and after a `term` update.  An update computes td as
+above, adds 1.0 to E[s][a], and then EVERY action b of EVERY visited state o
+contributes d = lr * (td * E[o][b]) to entry (update table, o, b), also where
+E is 0 (d = +-0, or NaN for a non-finite td); E[o][b] *= fl(gamma * lambda).
+Per group step there is ONE grid: code = the largest biased exponent over the
+FINITE tds of the group's updates (0 if none), e = max(code, 1) - 1075 +
+trace_k.  Every finite d is rounded half-to-even onto 2^e; the model raises if
+a rounded value reaches 2^51 (the one-add conversion's premise).  An entry's n
+is the number of (lane, visited state) pairs that covered its row, whatever
+their values, and the entry moves by ldexp(fl(float(sum) * fl(1.0 / n)), e).
+trace_k is trace_grid_k() below, DESIGN section 2 restated.
+
 Merge: an entry takes the mean over the groups whose final word differs
 BITWISE from Q_base's (so -0.0 against +0.0 is a change, and a group that moves
 an entry and brings it back to the same bits did not change it).  f64: the mean
@@ -56,20 +84,29 @@ changed finite value, h = max(0, ceil(log2(merge_groups)) - 10) headroom bits
 (also when one group changed the entry); non-finite values give the IEEE sum of
 their kinds.  fixed40: Q_base += trunc(float(sum of differences) * (1.0 / n)).
 UCB: N[s][a] += 1 for every selection (kind 1: the (s, a) of the reset; kind 2:
-(s2, a2)), t += 1 per selection, summed over all groups.
+(s2, a2)), t += 1 per selection; every group starts from the base and the
+launch's totals are the sums over all groups.
 
-The double-policy flag
-----------------------
+Per-lane state the caller carries
+---------------------------------
 rl_agent_lane_state documents `flags|a|mode` without naming the bits, so the
-flag is NOT read from there.  The caller counts: every lane starts with the
-flag true at rl_agent_create (DoubleTabularPolicy::new) and it flips once per
-update; `replay_launch` takes the flags before the launch and returns them
-after it, and the caller carries them from launch to launch.
+double-policy flag is NOT read from there.  Every lane starts with the flag
+true at rl_agent_create (DoubleTabularPolicy::new) and it flips once per
+update.  `replay_launch` takes flags, eps and traces before the launch and
+returns them after it (Replay.flags / .eps / .traces, and .last_eps for one
+coverage condition); the caller passes them to the next launch.
 
-Out of scope
-------------
-Eligibility traces (one grid per group step from trace_k; E is not recorded):
-`replay_launch(agent="traces")` raises, it does not approximate.
+ln
+--
+ln(t) is the one value the model cannot form: the project's log is an fdlibm
+sequence, not libm's.  `ln` is a callable int -> float supplied by the caller
+from the side under test; the tests check every value used against a 50-digit
+decimal logarithm (within 1 ulp), which makes it a checked scalar input.
+
+Outside the model
+-----------------
+Private mode (group_size 1) and the neural policy; the RNG, the envs and the
+selections themselves (records are the input).
 """
 import math
 import struct
@@ -81,8 +118,11 @@ QNAN_BITS = 0x7FF8000000000000
 NF_NAN, NF_PINF, NF_NINF = 1, 2, 4
 FIX_SHIFT = 40
 FIX_LIMIT = 1 << 51          # |Q| <= 2048 in units of 2^-40
+TRACE_RAW_LIMIT = 1 << 51    # the one-add conversion (y + 1.5 * 2^52) is exact below this
+MIN_POSITIVE = 2.0 ** -1022
 _M64 = (1 << 64) - 1
 _INF = float("inf")
+_NAN = float("nan")
 
 
 # ---------------------------------------------------------------- bit patterns
@@ -120,6 +160,10 @@ def nf_value(kinds):
     return _INF if kinds & NF_PINF else -_INF
 
 
+def _finite(x):
+    return x == x and x not in (_INF, -_INF)
+
+
 def grid_exponent(code):
     return max(code, 1) - 1075
 
@@ -133,9 +177,26 @@ def _pow2(e):
     return Fraction(1 << e) if e >= 0 else Fraction(1, 1 << -e)
 
 
+def on_grid_exact(x, e):
+    """(x / 2^e rounded half-to-even as an exact int, whether x was a multiple of
+    2^e).  Integers only: x = m * 2^q with m the 53-bit integer mantissa."""
+    fr, ex = math.frexp(x)
+    m = int(fr * 9007199254740992.0)          # fr * 2^53 is an integer, exactly
+    sh = ex - 53 - e
+    if sh >= 0:
+        return m << sh, True
+    s = -sh
+    q = m >> s                                # floor, also for negative m
+    rem = m - (q << s)                        # 0 <= rem < 2^s
+    half = 1 << (s - 1)
+    if rem > half or (rem == half and q & 1):
+        q += 1
+    return q, rem == 0
+
+
 def on_grid(x, e):
     """x / 2^e rounded half-to-even, as an exact int"""
-    return round(Fraction(x) / _pow2(e))
+    return on_grid_exact(x, e)[0]
 
 
 def _ldexp(m, e):
@@ -149,17 +210,62 @@ def grid_mean(total, n, e):
     return _ldexp(float(total) * (1.0 / n), e)
 
 
+# ---------------------------------------------------------------- IEEE helpers
+def ieee_div(a, b):
+    """a / b as IEEE 754 defines it where Python raises"""
+    if b == 0.0:
+        if a != a or a == 0.0:
+            return _NAN
+        return math.copysign(_INF, a) * math.copysign(1.0, b)
+    return a / b
+
+
+def ieee_sqrt(x):
+    if x != x or x < 0.0:
+        return _NAN
+    if x == _INF:
+        return _INF
+    return math.sqrt(x)               # sqrt(-0.0) is -0.0
+
+
+def trace_grid_k(lr, gamma, lam, max_steps, blackjack):
+    """DESIGN section 2 "Traces": the exponent k with 2^k > 4 * |lr| * Ebound * margin"""
+    a = abs(float(gamma) * float(lam))
+    if a < 1.0:
+        eb = 1.0 / (1.0 - a)
+    else:
+        n = 33 if blackjack else int(max_steps) + 2        # terms of the geometric sum
+        if a == 1.0:
+            eb = float(n)
+        else:
+            try:
+                eb = math.expm1(float(n) * math.log1p(a - 1.0)) / (a - 1.0)
+            except OverflowError:
+                eb = _INF
+    x = abs(float(lr)) * eb * (1.0 + 2.0 ** -50) * 1.0001
+    if not x > 0.0:
+        return 0
+    if not x < _INF:
+        return 1100
+    return max(-1100, min(1100, math.frexp(x)[1] + 2))
+
+
 # ---------------------------------------------------------------- events
 class StepEvent:
     """one entry in one group step: its contributions and the move taken.
     f64: ds / move in value units, e the grid exponent (None if a contribution
-    was non-finite).  fixed40: ds in value units, move an int of 2^-40."""
-    __slots__ = ("group", "step", "entry", "ds", "kinds", "e", "move", "before", "after")
+    was non-finite).  fixed40: ds in value units, move an int of 2^-40.
+    traces: Es the trace value behind every d, td_big the largest finite |td| of
+    the group step, inexact whether some d was no multiple of the grid."""
+    __slots__ = ("group", "step", "entry", "ds", "kinds", "e", "move", "before", "after", "Es", "td_big",
+                 "inexact")
 
-    def __init__(self, group, step, entry, ds, kinds, e, move, before, after):
+    def __init__(self, group, step, entry, ds, kinds, e, move, before, after, Es=None, td_big=None,
+                 inexact=False):
         self.group, self.step, self.entry = group, step, entry
         self.ds, self.kinds, self.e, self.move = ds, kinds, e, move
         self.before, self.after = before, after          # the entry's value / fixed-point word
+        self.Es, self.td_big, self.inexact = Es, td_big, inexact
 
 
 class MergeEvent:
@@ -174,8 +280,18 @@ class MergeEvent:
 
 
 class Replay:
-    __slots__ = ("words", "n", "t", "flags", "td_mismatches", "steps", "merges", "repr", "merge_groups",
-                 "n_groups")
+    __slots__ = ("words", "n", "t", "flags", "eps", "traces", "td_mismatches", "steps", "merges", "repr",
+                 "merge_groups", "n_groups", "agent", "trace_k", "max_raw_bits", "seen", "ln_used", "last_eps")
+
+
+class LaneTrace:
+    """a lane's eligibility trace: rows[s] = [E[s][0..A)] for the states visited
+    this episode, in first-visit order; last = the pairs taken in the episode
+    that the latest `term` cleared (coverage only)"""
+    __slots__ = ("rows", "last", "taken")
+
+    def __init__(self):
+        self.rows, self.last, self.taken = {}, set(), set()
 
 
 # ---------------------------------------------------------------- the model
@@ -187,35 +303,77 @@ def _first_max(row):
     return m
 
 
+def _argmax(row):
+    """utils.rs:1-11: a NaN at element 0 stays the maximum, a NaN elsewhere never wins"""
+    m, at = row[0], 0
+    for i, v in enumerate(row):
+        if v > m:
+            m, at = v, i
+    return at
+
+
 def _same_f64(a, b):
     return (a != a and b != b) or f64_bits(a) == f64_bits(b)
 
 
+def expected_eps_greedy(row2, eps):
+    A = len(row2)
+    p = [eps / float(A)] * A
+    p[_argmax(row2)] = 1.0 - eps
+    f = 0.0
+    for i in range(A):
+        f += p[i] * row2[i]
+    return f
+
+
+def expected_ucb(row2, counts, lnt, c):
+    u, total = [], 0.0
+    for q, n in zip(row2, counts):
+        ui = q + c * ieee_sqrt(ieee_div(lnt, float(n) + MIN_POSITIVE))
+        u.append(ui)
+        total += ui
+    f = 0.0
+    for ui, q in zip(u, row2):
+        f += ieee_div(ui, total) * q
+    return f
+
+
 def replay_launch(q_base, n_base, t_base, records, *, G, P, S, A, lr, gamma, algo, repr,
-                  merge_groups=0, ucb=False, flags=None, agent="one_step"):
-    """Predict Q_base's raw words and N / t after one launch.
+                  merge_groups=0, ucb=False, flags=None, agent="one_step", td_source="model",
+                  eps=None, eps_decay=0.0, eps_final=0.0, decay_kind=0, ucb_c=0.5, ln=None,
+                  lam=0.0, max_steps=0, blackjack=False, traces=None, last_eps=None):
+    """Predict Q_base's raw words, N / t and the lanes' epsilon after one launch.
 
     q_base: P*S*A int64 raw words ([P][S][A] order); n_base: S*A counts; t_base: int;
     records: [K][n_lanes] of rl_step_record (anything indexable by field name);
     algo: "sarsa" | "qlearning" | "expected_sarsa"; repr: "f64" | "fixed40";
+    agent: "one_step" | "traces"; td_source: "model" (recompute, report
+    td_mismatches) | "record" (the recorded td is the input);
     merge_groups: learner groups over every rank (0: this launch's own);
-    ucb: the selector is UCB (N / t move); flags: per-lane double-policy flag
-    before the launch (None: all true, the state at creation).
+    ucb: the selector is UCB (N / t move, ucb_c, ln(t) from the callable `ln`);
+    eps / eps_decay / eps_final / decay_kind: the eps-greedy selector's per-lane
+    epsilon before the launch and its decay (None: 0.0, for records without `term`);
+    lam / max_steps / blackjack: what the traces grid needs;
+    flags / traces: per-lane double-policy flag and LaneTrace before the launch
+    (None: the state at creation); last_eps: the epsilon of every lane's latest
+    expected-SARSA update (None where it made none; coverage only).
     """
-    if agent != "one_step":
-        raise NotImplementedError(
-            f"step_model replays the one-step agent only, not agent={agent!r}: eligibility "
-            "traces use one grid per group step and E is not recorded")
+    if agent not in ("one_step", "traces"):
+        raise ValueError(f"unknown agent {agent!r}")
     if algo not in ("sarsa", "qlearning", "expected_sarsa"):
         raise ValueError(f"unknown algo {algo!r}")
     if repr not in ("f64", "fixed40"):
         raise ValueError(f"unknown representation {repr!r}")
+    if td_source not in ("model", "record"):
+        raise ValueError(f"unknown td_source {td_source!r}")
     if P not in (1, 2) or G < 2 or G > 1024:
         raise ValueError("shared mode: P in {1, 2}, 2 <= group_size <= 1024")
-    if repr == "fixed40" and P != 1:
-        raise ValueError("the fixed point holds single tables only")
-    lr, gamma = float(lr), float(gamma)
+    if repr == "fixed40" and (P != 1 or agent != "one_step"):
+        raise ValueError("the fixed point holds single tables of the one-step agent only")
+    lr, gamma, lam, ucb_c = float(lr), float(gamma), float(lam), float(ucb_c)
     f64 = repr == "f64"
+    tr = agent == "traces"
+    es = algo == "expected_sarsa" and td_source == "model"
     nq = P * S * A
     base = [int(w) for w in q_base]
     if len(base) != nq:
@@ -226,6 +384,12 @@ def replay_launch(q_base, n_base, t_base, records, *, G, P, S, A, lr, gamma, alg
     total_groups = int(merge_groups) if merge_groups else n_groups
     h = headroom(total_groups)
     flags = [True] * L if flags is None else [bool(f) for f in flags]
+    eps = [0.0] * L if eps is None else [float(x) for x in eps]
+    traces = [LaneTrace() for _ in range(L)] if traces is None else list(traces)
+    if len(flags) != L or len(eps) != L or len(traces) != L:
+        raise ValueError("flags / eps / traces hold one value per lane")
+    gl = gamma * lam
+    trace_k = trace_grid_k(lr, gamma, lam, max_steps, blackjack) if tr else 0
 
     if f64:
         base_val = [f64_from_bits(w) for w in base]
@@ -237,63 +401,137 @@ def replay_launch(q_base, n_base, t_base, records, *, G, P, S, A, lr, gamma, alg
 
     out = Replay()
     out.repr, out.merge_groups, out.n_groups = repr, total_groups, n_groups
+    out.agent, out.trace_k, out.max_raw_bits = agent, trace_k, 0
     out.td_mismatches, out.steps, out.merges = [], [], []
-    n_after = [int(v) for v in n_base]
+    out.seen, out.ln_used = set(), {}
+    n_base = [int(v) for v in n_base]
+    n_after = list(n_base)
     t_after = int(t_base)
     finals = []                      # per group: {entry: final word}
+    last_eps = [None] * L if last_eps is None else list(last_eps)
 
     for g in range(n_groups):
         lane0, lane1 = g * G, min(L, (g + 1) * G)
         raw = {}                     # entry -> current word of this group (touched entries)
         val = {}                     # entry -> current value
+        n_inc, t_inc = {}, 0         # this group's own counter increments so far
 
         def V(tbl, s, a):
             i = (tbl * S + s) * A + a
             return val[i] if i in val else base_val[i]
 
         for k in range(K):
-            contrib = {}
-            for j in range(lane0, lane1):
-                rec = records[k][j]
-                kind = int(rec["kind"])
-                if kind == KIND_IDLE:
-                    continue
-                if ucb:
+            # every selection of the step moves the counters before any update reads them
+            step_inc = set()
+            if ucb:
+                for j in range(lane0, lane1):
+                    rec = records[k][j]
+                    kind = int(rec["kind"])
+                    if kind == KIND_IDLE:
+                        continue
                     if kind == KIND_RESET_STEP:
                         raise ValueError("the reset-and-step schedule does not exist with UCB")
                     sel = (int(rec["s"]), int(rec["a"])) if kind == KIND_RESET else \
                           (int(rec["s2"]), int(rec["a2"]))
-                    n_after[sel[0] * A + sel[1]] += 1
-                    t_after += 1
+                    i = sel[0] * A + sel[1]
+                    n_inc[i] = n_inc.get(i, 0) + 1
+                    t_inc += 1
+                    step_inc.add(sel[0])
+            contrib = {}             # entry -> [d]
+            contrib_E = {}           # entry -> [E] (traces)
+            rows = {}                # (table, state) -> lanes that covered the row (traces)
+            td_code, td_big = 0, 0.0
+            for j in range(lane0, lane1):
+                rec = records[k][j]
+                kind = int(rec["kind"])
                 if int(rec["mode"]) != MODE_TRAIN or kind not in (KIND_STEP, KIND_RESET_STEP):
                     continue
                 s, a, s2, a2 = int(rec["s"]), int(rec["a"]), int(rec["s2"]), int(rec["a2"])
                 r, td_rec = float(rec["r"]), float(rec["td"])
                 vt, ut = ((0, 1) if flags[j] else (1, 0)) if P == 2 else (0, 0)
-                if algo == "expected_sarsa":
+                if td_source == "record":
                     td = td_rec
                 else:
                     row2 = [V(vt, s2, i) for i in range(A)]
-                    nxt = row2[a2] if algo == "sarsa" else _first_max(row2)
+                    if algo == "sarsa":
+                        nxt = row2[a2]
+                    elif algo == "qlearning":
+                        nxt = _first_max(row2)
+                    elif ucb:
+                        t_now = int(t_base) + t_inc
+                        if t_now not in out.ln_used:
+                            out.ln_used[t_now] = float(ln(t_now))
+                        counts = [n_base[s2 * A + i] + n_inc.get(s2 * A + i, 0) for i in range(A)]
+                        nxt = expected_ucb(row2, counts, out.ln_used[t_now], ucb_c)
+                        if s2 in step_inc:
+                            out.seen.add("es_counts_moved_in_step")
+                    else:
+                        nxt = expected_eps_greedy(row2, eps[j])
+                        if last_eps[j] is not None and last_eps[j] != eps[j]:
+                            out.seen.add("es_eps_decayed_between_updates")
+                        last_eps[j] = eps[j]
+                    if es and not all(_finite(v) for v in row2):
+                        out.seen.add("es_nan_shortcut")
                     td = r + gamma * nxt - V(vt, s, a)
                     if not _same_f64(td, td_rec):
                         out.td_mismatches.append((g, k, j, td, td_rec))
-                contrib.setdefault((ut * S + s) * A + a, []).append(lr * td)
+                if not tr:
+                    contrib.setdefault((ut * S + s) * A + a, []).append(lr * td)
+                else:
+                    if _finite(td):
+                        td_code = max(td_code, biased_exponent(td))
+                        td_big = max(td_big, abs(td))
+                    lt = traces[j]
+                    row = lt.rows.setdefault(s, [0.0] * A)
+                    if row[a] != 0.0:
+                        out.seen.add("E_ge_2")
+                    if (s, a) in lt.last:
+                        out.seen.add("cleared_then_revisited")
+                    lt.taken.add((s, a))
+                    row[a] += 1.0
+                    for o, ev in lt.rows.items():
+                        rows[(ut, o)] = rows.get((ut, o), 0) + 1
+                        for b in range(A):
+                            i = (ut * S + o) * A + b
+                            contrib.setdefault(i, []).append(lr * (td * ev[b]))
+                            contrib_E.setdefault(i, []).append(ev[b])
+                            ev[b] *= gl
+                    if int(rec["term"]):
+                        lt.rows, lt.last, lt.taken = {}, lt.taken, set()
                 if P == 2:
                     flags[j] = not flags[j]
+                if not ucb and int(rec["term"]):
+                    nw = eps[j] * eps_decay if decay_kind == 1 else eps[j] - eps_decay
+                    if not eps_final > nw:
+                        eps[j] = nw
             # every lane read the step-start snapshot; now the entries move
+            e_tr = grid_exponent(td_code) + trace_k
             for i, ds in contrib.items():
                 n = len(ds)
+                inexact = False
+                if tr and n != rows[(i // A // S, i // A % S)]:
+                    raise AssertionError("an entry's contributions are not one per covering (lane, state)")
                 if f64:
                     kinds = 0
                     code = 0
                     for d in ds:
-                        if d != d or d in (_INF, -_INF):
+                        if not _finite(d):
                             kinds |= nf_kind(d)
                         else:
                             code = max(code, biased_exponent(d))
                     if kinds:
                         e, move = None, nf_value(kinds)
+                    elif tr:
+                        e, total = e_tr, 0
+                        for d in ds:
+                            x, exact = on_grid_exact(d, e)
+                            if abs(x) >= TRACE_RAW_LIMIT:
+                                raise ValueError(f"traces: a contribution is {abs(x).bit_length()} bits on the "
+                                                 "step grid, the one-add conversion needs |raw| < 2^51")
+                            out.max_raw_bits = max(out.max_raw_bits, abs(x).bit_length())
+                            inexact = inexact or not exact
+                            total += x
+                        move = grid_mean(total, n, e)
                     else:
                         e = grid_exponent(code)
                         move = grid_mean(sum(on_grid(d, e) for d in ds), n, e)
@@ -304,10 +542,10 @@ def replay_launch(q_base, n_base, t_base, records, *, G, P, S, A, lr, gamma, alg
                 else:
                     total = 0
                     for d in ds:
-                        if d != d or d in (_INF, -_INF):
+                        if not _finite(d):
                             raise ValueError("non-finite contribution in the fixed point: outside "
                                              "the proven range, the contract does not define it")
-                        x = round(Fraction(d) * (1 << FIX_SHIFT))
+                        x = on_grid(d, -FIX_SHIFT)
                         if abs(x) > FIX_LIMIT:
                             raise ValueError("fixed-point delta outside the proven range")
                         total += x
@@ -319,8 +557,12 @@ def replay_launch(q_base, n_base, t_base, records, *, G, P, S, A, lr, gamma, alg
                         raise ValueError("fixed-point entry outside the proven range")
                     raw[i] = new
                     val[i] = float(new) * 2.0 ** -FIX_SHIFT
-                out.steps.append(StepEvent(g, k, i, ds, kinds, e, move, old, new))
+                out.steps.append(StepEvent(g, k, i, ds, kinds, e, move, old, new, contrib_E.get(i),
+                                           td_big if tr else None, inexact))
         finals.append(raw)
+        for i, c in n_inc.items():
+            n_after[i] += c
+        t_after += t_inc
 
     # ---- merge
     words = list(base)
@@ -338,7 +580,7 @@ def replay_launch(q_base, n_base, t_base, records, *, G, P, S, A, lr, gamma, alg
                 kinds, code, fin = 0, 0, []
                 for w in changed:
                     v = f64_from_bits(w)
-                    if v != v or v in (_INF, -_INF):
+                    if not _finite(v):
                         kinds |= nf_kind(v)
                     else:
                         code = max(code, biased_exponent(v))
@@ -356,7 +598,8 @@ def replay_launch(q_base, n_base, t_base, records, *, G, P, S, A, lr, gamma, alg
                     raise ValueError("fixed-point entry outside the proven range")
         out.merges.append(MergeEvent(i, base[i], ws, changed, e, words[i]))
 
-    out.words, out.n, out.t, out.flags = words, n_after, t_after, flags
+    out.words, out.n, out.t, out.flags, out.eps, out.traces = words, n_after, t_after, flags, eps, traces
+    out.last_eps = last_eps
     return out
 
 
@@ -370,6 +613,8 @@ def replay_launch(q_base, n_base, t_base, records, *, G, P, S, A, lr, gamma, alg
 # double, 1/n and the product are three roundings (at most 3 * 2^-53 relative
 # < 2^-51); ldexp may round once more to a subnormal (at most 2^-1075):
 #     |move - mean| <= 2^(e-1) + 2^-51 * |mean| + 2^-1075
+# traces step: the same bound with e the grid of the step's largest finite |td|
+# (frexp) plus trace_k.
 # f64 merge: the same with the values v_g and e + headroom.
 # fixed40 step (units of 2^-40): rint of each d_i is at most half a unit and
 # trunc loses less than one whole unit more, so the bound is 3/2 units + the
@@ -410,7 +655,10 @@ def step_accuracy(replay):
         n = len(ev.ds)
         mean = sum(Fraction(d) for d in ev.ds) / n
         if replay.repr == "f64":
-            e = _natural_grid(ev.ds)
+            if replay.agent == "traces":
+                e = _natural_grid([ev.td_big]) + replay.trace_k
+            else:
+                e = _natural_grid(ev.ds)
             rows.append(_check_row(mean, ev.move, _pow2(e - 1) + _REL * abs(mean) + _TINY))
         else:
             unit = _pow2(-FIX_SHIFT)
@@ -431,7 +679,7 @@ def merge_accuracy(replay):
         n = len(ev.changed)
         if replay.repr == "f64":
             vs = [f64_from_bits(w) for w in ev.changed]
-            if any(v != v or v in (_INF, -_INF) for v in vs):
+            if any(not _finite(v) for v in vs):
                 continue
             mean = sum(Fraction(v) for v in vs) / n
             e = _natural_grid(vs) + h
@@ -446,22 +694,41 @@ def merge_accuracy(replay):
 
 
 # ---------------------------------------------------------------- coverage
+TRACE_CONDITIONS = ("row_count_exceeds_nonzero", "decayed_E", "E_ge_2", "cleared_then_revisited", "grid_rounded",
+                    "nonfinite_zero_E")
+ES_CONDITIONS = ("es_eps_decayed_between_updates", "es_counts_moved_in_step", "es_nan_shortcut")
+
+
 def coverage(replay):
-    """which edges this launch exercised (conditions, computed from the events)"""
+    """which edges this launch exercised (conditions, computed from the events and
+    from what the replay saw on its way)"""
     c = dict.fromkeys(("codes_54_apart", "subnormal_grid", "pinf_with_ninf", "finite_with_nonfinite",
                        "n_ge_64", "changed_by_2_groups", "changed_and_unchanged", "touched_back_to_base",
-                       "sign_of_zero_change", "step_overflow", "merge_nonfinite"), False)
+                       "sign_of_zero_change", "step_overflow", "merge_nonfinite") + TRACE_CONDITIONS
+                      + ES_CONDITIONS, False)
+    for name in replay.seen:
+        c[name] = True
     for ev in replay.steps:
         n = len(ev.ds)
         if n >= 64:
             c["n_ge_64"] = True
         if replay.repr != "f64":
             continue
-        fin = [d for d in ev.ds if d == d and d not in (_INF, -_INF)]
+        fin = [d for d in ev.ds if _finite(d)]
         if ev.kinds & NF_PINF and ev.kinds & NF_NINF:
             c["pinf_with_ninf"] = True
         if ev.kinds and fin:
             c["finite_with_nonfinite"] = True
+        if ev.Es is not None:
+            nonzero = sum(1 for d in ev.ds if d != 0.0)
+            if 0 < nonzero < n:
+                c["row_count_exceeds_nonzero"] = True
+            if any(E != math.floor(E) for E in ev.Es):
+                c["decayed_E"] = True
+            if ev.inexact:
+                c["grid_rounded"] = True
+            if any(E == 0.0 and d != d for E, d in zip(ev.Es, ev.ds)):
+                c["nonfinite_zero_E"] = True
         if not ev.kinds:
             codes = [biased_exponent(d) for d in fin]
             if n >= 2 and max(codes) - min(codes) >= 54:
@@ -483,6 +750,6 @@ def coverage(replay):
                 v = f64_from_bits(w)
                 if v == b:                       # equal as numbers, different bits: -0.0 / +0.0
                     c["sign_of_zero_change"] = True
-                if v != v or v in (_INF, -_INF):
+                if not _finite(v):
                     c["merge_nonfinite"] = True
     return c

@@ -3,17 +3,22 @@ model (tests/step_model.py): the cases, tables and helper of
 tests/test_step_model.py, driven on rl.Agent instead of the CPU oracle.
 
 Every launch is replayed from the device's own rl_step_record entries: the
-model's raw Q words and UCB counters must equal the device's, every td
-recomputed from the group's step-start snapshot must equal the recorded one,
-and the coverage conditions must hold on the device's records.  No oracle call
-is made here, so a mistake shared by the oracle and the kernels cannot hide.
+model's raw Q words, UCB counters and per-lane epsilon must equal the device's,
+every td recomputed from the group's step-start snapshot must equal the recorded
+one (expected SARSA's with the device's own log, rl_kat_log, checked against a
+50-digit logarithm), and the coverage conditions must hold on the device's
+records.  The traces and expected-SARSA combinations of the parity matrix and the
+edge cases run here as they do on the oracle.  No oracle call is made here, so a
+mistake shared by the oracle and the kernels cannot hide.
 """
 import ctypes as C
 
 import numpy as np
 import pytest
 
-from test_step_model import (CASES, COMMON, HEADROOM_CASE, ONE_LANE, assert_coverage, crafted_table,
+import matrix_cases as mc
+from test_step_model import (CASES, COMMON, EDGE_CASES, EDGE_COMMON, HEADROOM_CASE, MATRIX, MATRIX_FIXED, ONE_LANE,
+                             assert_coverage, check_edge_case, check_matrix_case, crafted_table,
                              one_lane_plain_update, replay_and_check, setup_pair)
 
 pytestmark = pytest.mark.gpu
@@ -76,5 +81,46 @@ def test_device_one_lane_is_plain_update(rl, name):
         dev.set_q_mode("f64")
         dev.set_recording(True)
         one_lane_plain_update(dev, p)
+    finally:
+        dev.close()
+
+
+# ---------------------------------------------------------------- traces and expected SARSA
+# Blackjack's double policy under UCB does not fit a learner group's LDS
+# (matrix_cases.shared_rejected; tests/test_gpu_matrix.py asserts the rejection)
+DEVICE_MATRIX = [c for c in MATRIX if not mc.shared_rejected(c)]
+assert len(DEVICE_MATRIX) == 156         # four of the six rejected combinations are among the 160
+
+
+def device_ln(rl):
+    return lambda ts: rl.kat_log(np.asarray(ts, np.float64)).tolist()
+
+
+@pytest.mark.parametrize("c", DEVICE_MATRIX, ids=mc.case_id)
+def test_device_matrix_case_equals_replay_model(rl, c):
+    p = mc.device_params(rl, mc.shared_kw(c), c)
+    dev = rl.Agent(p)
+    try:
+        check_matrix_case(dev, p, c, device_ln(rl))
+    finally:
+        dev.close()
+
+
+@pytest.mark.parametrize("c", MATRIX_FIXED, ids=mc.case_id)
+def test_device_matrix_case_forced_f64_equals_replay_model(rl, c):
+    p = mc.device_params(rl, mc.shared_kw(c), c)
+    dev = rl.Agent(p)
+    try:
+        check_matrix_case(dev, p, c, device_ln(rl), q_mode="f64")
+    finally:
+        dev.close()
+
+
+@pytest.mark.parametrize("name", list(EDGE_CASES))
+def test_device_edge_case_equals_replay_model(rl, name):
+    p = rl.default_params(**EDGE_COMMON, **EDGE_CASES[name][0])
+    dev = rl.Agent(p)
+    try:
+        check_edge_case(dev, p, name, device_ln(rl))
     finally:
         dev.close()

@@ -8,12 +8,22 @@ counter; tests/test_gpu_step_model.py drives the device through the same
 helper.  The accuracy rows state what "summed exactly on the grid" promises
 against the exact rational mean, and the coverage conditions keep every case on
 the edge it was built for (they are asserted, not reported).
+
+The model recomputes every td (expected SARSA's included: per-lane epsilon,
+the group's running UCB counters, ln(t) of the side under test checked against
+a 50-digit logarithm) and replays eligibility traces; the hand-worked tests
+below pin the model itself word by word, and the live cases run every traces /
+expected-SARSA combination of the parity matrix plus the edges it lacks.
+Measured on the CPU: the slowest live case (Taxi, traces, double, UCB) takes
+0.7 s, almost all of it the model.
 """
+import decimal
 import math
 
 import numpy as np
 import pytest
 
+import matrix_cases as mc
 import step_model as sm
 
 LAUNCHES = 3
@@ -114,14 +124,44 @@ def _first_diffs(got, want, limit=5):
     return len(bad), bad[:limit]
 
 
-def replay_and_check(obj, p, launch, *, launches=LAUNCHES, merge_groups=0):
+_LN_CHECKED = {}
+
+
+def assert_ln_within_1ulp(used):
+    """every ln(t) the model was given against a 50-digit decimal logarithm: the
+    side under test's log is an input of the model, and this makes it a checked one"""
+    ctx = decimal.Context(prec=50)
+    for t, v in used.items():
+        if _LN_CHECKED.get(t) == v:
+            continue
+        if t == 1:
+            assert v == 0.0
+        else:
+            exact = ctx.ln(decimal.Decimal(t))
+            err = abs(ctx.subtract(decimal.Decimal(v), exact))
+            assert err <= decimal.Decimal(math.ulp(v)), f"ln({t}) = {v!r} is more than 1 ulp from {exact}"
+        _LN_CHECKED[t] = v
+
+
+def model_kw(obj, p):
+    """what replay_launch needs of the parameters"""
+    return dict(G=p["group_size"], P=obj.P, S=obj.S, A=obj.A, lr=p["lr"], gamma=p["gamma"], algo=p["algo"],
+                ucb=p["selector"] == "ucb", agent=p["agent"], eps_decay=p["eps_decay"], eps_final=p["eps_final"],
+                decay_kind=p["decay_kind"], ucb_c=p["ucb_c"], lam=p["lambda_"], max_steps=p["max_steps"],
+                blackjack=p["env"] in ("blackjack", 3))
+
+
+def replay_and_check(obj, p, launch, *, launches=LAUNCHES, merge_groups=0, ln=None, info=None):
     """Run `launches` launches on obj (an oracle Batch or a device Agent, recording
-    on), replay each from its records and assert the model's words and counters
-    equal obj's, the recomputed td equal the recorded ones and the accuracy rows
-    hold.  Returns the coverage conditions met over all launches."""
-    S, A, P = obj.S, obj.A, obj.P
-    ucb = p["selector"] == "ucb"
-    flags = None                       # every lane's double-policy flag starts true
+    on), replay each from its records and assert the model's words, counters and
+    per-lane epsilon equal obj's, the recomputed td equal the recorded ones and the
+    accuracy rows hold.  ln: the log of obj's side, a list of ints -> list of floats
+    (called once per launch; needed for UCB + expected SARSA only).  Returns the
+    coverage conditions met over all launches; info (a dict) receives max_raw_bits."""
+    kw = model_kw(obj, p)
+    needs_ln = kw["ucb"] and p["algo"] == "expected_sarsa"
+    flags = traces = last_eps = None   # the state at creation
+    eps = np.asarray(obj.epsilon(), np.float64).tolist()
     met = {}
     for li in range(launches):
         q0 = obj.q_raw().reshape(-1).tolist()
@@ -130,15 +170,22 @@ def replay_and_check(obj, p, launch, *, launches=LAUNCHES, merge_groups=0):
         launch()
         recs = obj.records()
         assert recs.shape == (p["sync_every"], p["n_lanes"])
-        rep = sm.replay_launch(q0, n0, int(t0), _records_as_dicts(recs), G=p["group_size"], P=P, S=S, A=A,
-                               lr=p["lr"], gamma=p["gamma"], algo=p["algo"], repr=obj.q_repr(),
-                               merge_groups=merge_groups, ucb=ucb, flags=flags, agent=p["agent"])
-        flags = rep.flags
+        table = {}
+        if needs_ln:
+            # a group's t runs from t0 to t0 + one increment per lane and step
+            ts = list(range(int(t0), int(t0) + p["sync_every"] * min(p["group_size"], p["n_lanes"]) + 1))
+            table = dict(zip(ts, (float(v) for v in ln(ts))))
+        rep = sm.replay_launch(q0, n0, int(t0), _records_as_dicts(recs), repr=obj.q_repr(), merge_groups=merge_groups,
+                               flags=flags, eps=eps, traces=traces, last_eps=last_eps, ln=table.__getitem__, **kw)
+        flags, eps, traces, last_eps = rep.flags, rep.eps, rep.traces, rep.last_eps
+        assert_ln_within_1ulp(rep.ln_used)
         assert not rep.td_mismatches, f"launch {li}: td recomputed != recorded: {rep.td_mismatches[:5]}"
         nbad, bad = _first_diffs(obj.q_raw().reshape(-1).tolist(), rep.words)
         assert nbad == 0, f"launch {li}: {nbad} Q words differ (entry, got, model): {bad}"
         n1, t1 = obj.ucb()
         assert np.asarray(n1).reshape(-1).tolist() == rep.n and int(t1) == rep.t, f"launch {li}: UCB counters"
+        got_eps = np.asarray(obj.epsilon(), np.float64)
+        assert got_eps.view(np.uint64).tolist() == [sm.f64_bits(x) for x in rep.eps], f"launch {li}: epsilon"
         for name, rows in (("step", sm.step_accuracy(rep)), ("merge", sm.merge_accuracy(rep))):
             worst = [r for r in rows if not r[3]]
             assert not worst, f"launch {li}: {name} accuracy bound missed (mean, got, bound): " \
@@ -146,12 +193,13 @@ def replay_and_check(obj, p, launch, *, launches=LAUNCHES, merge_groups=0):
         for k, v in sm.coverage(rep).items():
             met[k] = met.get(k, False) or v
         met["kind3"] = met.get("kind3", False) or bool((recs["kind"] == 3).any())
+        if info is not None:
+            info["max_raw_bits"] = max(info.get("max_raw_bits", 0), rep.max_raw_bits)
         if merge_groups and sm.headroom(merge_groups):
             # the same launch merged without headroom must differ somewhere, or the
             # headroom bits were never visible in this case
-            plain = sm.replay_launch(q0, n0, int(t0), _records_as_dicts(recs), G=p["group_size"], P=P, S=S,
-                                     A=A, lr=p["lr"], gamma=p["gamma"], algo=p["algo"], repr=obj.q_repr(),
-                                     merge_groups=0, ucb=ucb, flags=None, agent=p["agent"]) if P == 1 else None
+            plain = sm.replay_launch(q0, n0, int(t0), _records_as_dicts(recs), repr=obj.q_repr(), merge_groups=0,
+                                     **kw) if obj.P == 1 and p["agent"] == "one_step" else None
             if plain is not None and plain.words != rep.words:
                 met["headroom_moves_result"] = True
     return met
@@ -252,12 +300,6 @@ def one_lane_plain_update(obj, p, launches=8):
 
 
 # ---------------------------------------------------------------- the model itself
-def test_model_refuses_traces():
-    with pytest.raises(NotImplementedError, match="traces"):
-        sm.replay_launch([0] * 4, [0] * 4, 1, [], G=2, P=1, S=2, A=2, lr=0.1, gamma=0.9, algo="sarsa",
-                         repr="f64", agent="traces")
-
-
 def test_model_imports_neither_oracle_nor_library():
     import ast
     tree = ast.parse(open(sm.__file__).read())
@@ -278,16 +320,16 @@ def test_ldexp_rounds_subnormals_half_to_even():
     assert math.copysign(1.0, math.ldexp(-0.25, -1074)) == -1.0
 
 
-def _rec(kind=2, s=0, a=0, s2=1, a2=0, r=0.0, td=0.0, mode=0):
-    return dict(kind=kind, s=s, a=a, s2=s2, a2=a2, r=r, td=td, mode=mode, term=0)
+def _rec(kind=2, s=0, a=0, s2=1, a2=0, r=0.0, td=0.0, mode=0, term=0):
+    return dict(kind=kind, s=s, a=a, s2=s2, a2=a2, r=r, td=td, mode=mode, term=term)
 
 
 def _replay_td(tds, lr=1.0, base=0.0, **kw):
-    """G lanes each contributing lr * td to entry (0, 0) in one step (expected
-    SARSA takes the recorded td as its input)"""
+    """G lanes each contributing lr * td to entry (0, 0) in one step (the recorded
+    td is the input: td_source="record")"""
     words = [sm.f64_word(base), 0, 0, 0]
     return sm.replay_launch(words, [0] * 4, 1, [[_rec(td=t) for t in tds]], G=max(2, len(tds)), P=1, S=2, A=2,
-                            lr=lr, gamma=0.5, algo="expected_sarsa", repr="f64", **kw)
+                            lr=lr, gamma=0.5, algo="sarsa", repr="f64", td_source="record", **kw)
 
 
 def test_model_hand_worked_edges():
@@ -328,3 +370,300 @@ def test_accuracy_rows_reject_a_wrong_grid():
     assert all(r[3] for r in sm.merge_accuracy(rep))
     rep.merges[0].merged = sm.f64_word(1.0 + 16 * 2.0 ** -52)     # 4 bits dropped instead of 2
     assert not all(r[3] for r in sm.merge_accuracy(rep))
+
+
+# ---------------------------------------------------------------- hand-worked: traces
+# lr 0.5, gamma 0.5, lambda 0.5: fl(gamma * lambda) = 0.25, Ebound = 1 / 0.75, and
+# 0.5 * 1.333 * (1 + 2^-50) * 1.0001 = 0.6667.. = 0.6667 * 2^0, so trace_k = 0 + 2 = 2:
+# a step whose largest |td| is 1.0 (code 1023) runs on the grid 2^(1023 - 1075 + 2) = 2^-50.
+def _traces(records, S=2, P=1, lr=0.5, gamma=0.5, lam=0.5, max_steps=100, q=None, **kw):
+    words = [sm.f64_word(v) for v in (q or [0.0] * (P * S * 2))]
+    G = max(2, len(records[0]))
+    return sm.replay_launch(words, [0] * (S * 2), 1, records, G=G, P=P, S=S, A=2, lr=lr, gamma=gamma,
+                            algo="sarsa", repr="f64", agent="traces", td_source="record", lam=lam,
+                            max_steps=max_steps, **kw)
+
+
+def _values(rep):
+    return [sm.f64_from_bits(w) for w in rep.words]
+
+
+def test_trace_grid_k_by_hand():
+    assert sm.trace_grid_k(0.5, 0.5, 0.5, 100, False) == 2
+    # gamma * lambda = 1: Ebound is the max_steps + 2 = 4 terms; 0.5 * 4 * 1.0001.. = 0.50005 * 2^2: k = 4
+    assert sm.trace_grid_k(0.5, 1.0, 1.0, 2, False) == 4
+    # Blackjack has 33 terms whatever max_steps says: 33 * 1.0001 = 0.5157 * 2^6: k = 8
+    assert sm.trace_grid_k(1.0, 1.0, 1.0, 2, True) == 8
+    # above 1: (1.5^4 - 1) / 0.5 = 8.125, times 0.5 * 1.0001 = 4.06 = 0.508 * 2^3: k = 5
+    assert sm.trace_grid_k(0.5, 1.0, 1.5, 2, False) == 5
+    assert sm.trace_grid_k(0.0, 0.5, 0.5, 100, False) == 0
+    assert sm.trace_grid_k(1e300, 1.0, 10.0, 10 ** 6, False) == 1100        # the sum overflows
+
+
+def test_traces_row_count_includes_a_zero_E_action():
+    """lane 0 takes (0, 0), lane 1 takes (0, 1), both td 1.0: both lanes cover row 0,
+    so entry (0, 0) receives 0.5 * (1 * 1) and 0.5 * (1 * 0) and n = 2: it moves by
+    0.25.  Counting only the non-zero contribution would move it by 0.5."""
+    rep = _traces([[_rec(s=0, a=0, td=1.0), _rec(s=0, a=1, td=1.0)]])
+    assert _values(rep) == [0.25, 0.25, 0.0, 0.0]
+    assert sm.coverage(rep)["row_count_exceeds_nonzero"]
+    assert all(r[3] for r in sm.step_accuracy(rep))
+
+
+def test_traces_grid_comes_from_the_steps_largest_td():
+    """lane 0's td 2^30 (code 1053) puts the whole step on 2^(1053 - 1075 + 2) = 2^-20.
+    Lanes 1 and 2 contribute 0.5 + 2^-21 (2^19 + 0.5 units: the tie goes to the even
+    2^19) and 0.5 + 3 * 2^-21 (2^19 + 1.5 units: up to 2^19 + 2) to entries of their
+    own; on those entries' own grids both would be stored exactly."""
+    rep = _traces([[_rec(s=0, a=0, td=2.0 ** 30), _rec(s=1, a=0, td=1.0 + 2.0 ** -20),
+                    _rec(s=2, a=0, td=1.0 + 3 * 2.0 ** -20)]], S=3)
+    assert _values(rep) == [2.0 ** 29, 0.0, 0.5, 0.0, 0.5 + 2.0 ** -19, 0.0]
+    assert sm.coverage(rep)["grid_rounded"] and rep.steps[0].e == -20
+    assert all(r[3] for r in sm.step_accuracy(rep))
+    assert rep.max_raw_bits == 50                        # 2^29 / 2^-20 = 2^49
+    # the accuracy row takes its grid from the td, not from the combine: a move on
+    # the entries' own grid is as far from it as a rounding on 2^-18 would be
+    rep.steps[2].move = 0.5 + 2.0 ** -18
+    assert not all(r[3] for r in sm.step_accuracy(rep))
+
+
+def test_traces_E_accumulates_and_decays_between_visits():
+    """one lane, td 1.0 each step, visits (0,0), (1,0), (0,0):
+    step 0: Q00 += 0.5 * 1;                         E00 = 1 -> 0.25
+    step 1: Q00 += 0.5 * 0.25, Q10 += 0.5 * 1;      E00 -> 0.0625, E10 = 1 -> 0.25
+    step 2: E00 = 1.0625: Q00 += 0.53125, Q10 += 0.5 * 0.25
+    Q00 = 1.15625, Q10 = 0.625 (replacing traces: 1.125; no decay: 2.0)."""
+    rep = _traces([[_rec(s=0, a=0, td=1.0)], [_rec(s=1, a=0, td=1.0)], [_rec(s=0, a=0, td=1.0)]])
+    assert _values(rep) == [1.15625, 0.0, 0.625, 0.0]
+    cov = sm.coverage(rep)
+    assert cov["decayed_E"] and cov["E_ge_2"]
+    # gamma * lambda = 1, max_steps 2 (trace_k 4): E is exactly 2 at the revisit,
+    # Q00 = 0.5 * 1 + 0.5 * 2 = 1.5
+    rep = _traces([[_rec(s=0, a=0, s2=0, td=1.0)], [_rec(s=0, a=0, td=1.0)]], gamma=1.0, lam=1.0, max_steps=2)
+    assert _values(rep) == [1.5, 0.0, 0.0, 0.0] and rep.steps[2].Es == [2.0] and rep.steps[0].e == -48
+
+
+def test_traces_E_is_cleared_at_term():
+    """(0,0) with term, a reset, (0,0) again: the second visit starts from E = 0, so
+    Q00 = 0.5 + 0.5 = 1.0; a trace kept over the episode's end would give 0.5 + 0.625.
+    The state carried to the next launch is the trace after its decay."""
+    rep = _traces([[_rec(s=0, a=0, td=1.0, term=1)], [_rec(kind=1, s=0, a=0)], [_rec(s=0, a=0, td=1.0)]])
+    assert _values(rep) == [1.0, 0.0, 0.0, 0.0]
+    assert sm.coverage(rep)["cleared_then_revisited"]
+    assert rep.traces[0].rows == {0: [0.25, 0.0]}
+    nxt = _traces([[_rec(s=1, a=1, td=1.0)]], traces=rep.traces)
+    assert _values(nxt) == [0.125, 0.0, 0.0, 0.5]        # 0.5 * (1 * 0.25) for the carried pair
+
+
+def test_traces_nonfinite_td_makes_the_untaken_action_nan():
+    """td = +inf at (0, 0): 0.5 * (inf * 1) = +inf for the taken action and
+    0.5 * (inf * 0) = NaN for action 1 of the same state, which the lane never took"""
+    rep = _traces([[_rec(s=0, a=0, td=float("inf"))]])
+    assert rep.words == [sm.f64_word(float("inf")), sm.QNAN_BITS, 0, 0]
+    assert sm.coverage(rep)["nonfinite_zero_E"]
+
+
+def test_traces_double_update_goes_to_the_flagged_table():
+    """the flag starts true: the first update writes table 1, the second table 0,
+    with one trace for both.  T1[0][0] = 0.5; then T0[0][0] = 0.5 * 0.25, T0[1][0] = 0.5."""
+    rep = _traces([[_rec(s=0, a=0, td=1.0)], [_rec(s=1, a=0, td=1.0)]], P=2)
+    assert _values(rep) == [0.125, 0.0, 0.5, 0.0, 0.5, 0.0, 0.0, 0.0]
+    assert rep.flags == [True]
+
+
+def test_traces_breach_of_the_one_add_premise_is_an_error():
+    """a contribution of 2^51 grid units: the model raises, it does not round on"""
+    lt = sm.LaneTrace()
+    lt.rows = {0: [8.0, 0.0]}                 # E = 9 at the update: 0.5 * 9 / 2^-50 = 2^51 * 1.125
+    with pytest.raises(ValueError, match="2\\^51"):
+        _traces([[_rec(s=0, a=0, td=1.0)]], traces=[lt])
+
+
+# ---------------------------------------------------------------- hand-worked: expected SARSA
+def _es(records, q, **kw):
+    kw = dict(dict(lr=1.0, gamma=1.0), **kw)
+    return sm.replay_launch([sm.f64_word(v) for v in q], kw.pop("n0", [0] * 4), kw.pop("t0", 1), records,
+                            G=max(2, len(records[0])), P=1, S=2, A=2, algo="expected_sarsa", repr="f64", **kw)
+
+
+def test_expected_sarsa_reads_epsilon_before_its_decay():
+    """row 1 = [1, 3], eps 0.5 with a linear decay of 0.25.  The terminal update of
+    (0, 0) reads eps 0.5: p = [0.25, 0.5], f = 0.25 + 1.5 = 1.75 = td.  With the
+    decayed 0.25 it would be p = [0.125, 0.75], f = 2.375 — which is what the lane's
+    next update, of (0, 1) after the reset, gets."""
+    recs = [[_rec(s=0, a=0, s2=1, td=1.75, term=1)], [_rec(kind=1, s=0, a=1)], [_rec(s=0, a=1, s2=1, td=2.375)]]
+    rep = _es(recs, [0.0, 0.0, 1.0, 3.0], eps=[0.5], eps_decay=0.25)
+    assert not rep.td_mismatches
+    assert _values(rep) == [1.75, 2.375, 1.0, 3.0] and rep.eps == [0.25]
+    assert sm.coverage(rep)["es_eps_decayed_between_updates"]
+    # eps_final above the decayed value keeps epsilon; decay_kind 1 multiplies
+    assert _es(recs, [0.0, 0.0, 1.0, 3.0], eps=[0.5], eps_decay=0.25, eps_final=0.3).eps == [0.5]
+    assert _es(recs, [0.0, 0.0, 1.0, 3.0], eps=[0.5], eps_decay=0.25, decay_kind=1).eps == [0.125]
+
+
+def test_expected_sarsa_ucb_reads_the_counters_after_the_steps_selections():
+    """two lanes select (1, 0) in the same step: the group's N[1] goes from [2, 1] to
+    [4, 1] and t from 1 to 3 before either update reads them.  With ln(3) given as 4.0
+    (ln is an input; any function shows which t and n are read) and c = 1:
+    u = [0 + sqrt(4 / 4), 1 + sqrt(4 / 1)] = [1, 3], sum 4, p = [0.25, 0.75],
+    f = 0.75 = td for both lanes.  The step-start counters (t = 1, n = [2, 1]) or the
+    lane's own increment alone (t = 2, n = [3, 1]) give other numbers."""
+    recs = [[_rec(s=0, a=0, s2=1, a2=0, td=0.75), _rec(s=0, a=1, s2=1, a2=0, td=0.75)]]
+    rep = _es(recs, [0.0, 0.0, 0.0, 1.0], ucb=True, ucb_c=1.0, n0=[0, 0, 2, 1], t0=1,
+              ln={1: 1.0, 2: 2.0, 3: 4.0}.__getitem__)
+    assert not rep.td_mismatches
+    assert _values(rep) == [0.75, 0.75, 0.0, 1.0]
+    assert rep.n == [0, 0, 4, 1] and rep.t == 3 and rep.ln_used == {3: 4.0}
+    assert sm.coverage(rep)["es_counts_moved_in_step"]
+
+
+def test_nan_at_action_0_is_the_argmax():
+    nan = float("nan")
+    assert sm._argmax([nan, 5.0]) == 0 and sm._argmax([1.0, nan, 0.5]) == 0 and sm._argmax([1.0, nan, 2.0]) == 2
+    assert sm._argmax([3.0, 3.0]) == 0
+    # eps 0.5, row [NaN, 5]: p[0] = 0.5 is the greedy weight, f = 0.5 * NaN + 0.25 * 5 = NaN
+    rep = _es([[_rec(s=0, a=0, s2=1, td=nan)]], [0.0, 0.0, nan, 5.0], eps=[0.5])
+    assert not rep.td_mismatches and rep.words[0] == sm.QNAN_BITS
+    assert sm.coverage(rep)["es_nan_shortcut"]
+    # p[argmax] = 1 - eps and the others eps / A: row [1, 3], eps 0.5 -> 0.25 * 1 + 0.5 * 3
+    assert sm.expected_eps_greedy([1.0, 3.0], 0.5) == 1.75 and sm.expected_eps_greedy([3.0, 1.0], 0.5) == 1.75
+
+
+def test_zero_ucb_sum_is_nan_by_ieee_division():
+    """c = 0 and a zero row: u = [0, 0], sum 0, p = 0 / 0 = NaN where Python's own
+    division raises; the td and the entry are NaN"""
+    rep = _es([[_rec(s=0, a=0, s2=1, td=float("nan"))]], [0.0, 0.0, 0.0, 0.0], ucb=True, ucb_c=0.0,
+              n0=[0, 0, 1, 1], ln=math.log)
+    assert not rep.td_mismatches and rep.words[0] == sm.QNAN_BITS
+    inf = float("inf")
+    assert sm.ieee_div(1.0, 0.0) == inf and sm.ieee_div(-1.0, 0.0) == -inf and sm.ieee_div(1.0, -0.0) == -inf
+    assert sm.ieee_div(0.0, 0.0) != sm.ieee_div(0.0, 0.0) and sm.ieee_div(inf, inf) != sm.ieee_div(inf, inf)
+    assert sm.ieee_sqrt(-1.0) != sm.ieee_sqrt(-1.0) and sm.ieee_sqrt(inf) == inf
+    # fresh counters: ln(55) / 2^-1022 overflows to +inf, an unvisited action's bonus
+    assert sm.ieee_div(math.log(55.0), sm.MIN_POSITIVE) == inf and sm.ieee_div(math.log(54.0), sm.MIN_POSITIVE) < inf
+
+
+def test_on_grid_is_the_rational_rounding():
+    """the integer-only rounding against Fraction division, ties and signs included"""
+    from fractions import Fraction
+    rs = np.random.RandomState(3)
+    xs = [0.0, -0.0, 0.5, 1.5, 2.5, -0.5, -1.5, -2.5, 2.0 ** -1074, -3 * 2.0 ** -1074, 1.7976931348623157e308]
+    xs += list(np.ldexp(rs.uniform(-1, 1, 200), rs.randint(-60, 60, 200)))
+    for x in xs:
+        for e in (-1074, -60, -3, -1, 0, 1, 5, 40):
+            want = round(Fraction(float(x)) / (Fraction(2) ** e))
+            got, exact = sm.on_grid_exact(float(x), e)
+            assert got == want and exact == (Fraction(float(x)) == want * Fraction(2) ** e), (x, e)
+
+
+def test_trace_grid_k_equals_the_oracles(oracle):
+    """the documented formula in CPython floats against rlo_trace_grid_k"""
+    L = oracle.lib()
+    one_up = 1.0 + 2.0 ** -52
+    n = 0
+    for lr in (0.0, 1e-300, 1e-30, 0.05, 0.5, 1.0, 3.0, 1e30, 1e300, -0.05):
+        for gamma, lam in ((0.95, 0.5), (0.5, 0.5), (0.99, 0.999), (1.0, 1.0 - 2.0 ** -53), (1.0, 1.0), (1.0, one_up),
+                           (1.0, 1.5), (1.0, 10.0), (0.9, 0.0), (-1.0, 1.0), (1.0, -1.5), (2.0, 0.5)):
+            for max_steps in (1, 6, 20, 100, 10 ** 6, 2 ** 32 - 1):
+                for env in ("cliff_walking", "blackjack"):
+                    want = L.rlo_trace_grid_k(lr, gamma, lam, max_steps, oracle.ENV[env])
+                    got = sm.trace_grid_k(lr, gamma, lam, max_steps, env == "blackjack")
+                    assert got == want, (lr, gamma, lam, max_steps, env, got, want)
+                    n += 1
+    assert n == 1440
+
+
+# ---------------------------------------------------------------- live: traces and expected SARSA
+# every shared combination of the parity matrix (tests/matrix_cases.py) whose agent
+# is the traces one or whose algorithm is expected SARSA: 160 of the 240, at the
+# matrix's geometry (130 lanes in groups of 64, 64 and 2, K 8, q_default 0.25, preset
+# counters for UCB + expected SARSA), 2 launches from creation.
+MATRIX = [c for c in mc.combos() if c[1] == "traces" or c[4] == "expected_sarsa"]
+# AUTO holds these in the fixed point; they run once more forced to f64
+MATRIX_FIXED = [c for c in MATRIX if c[0] in ("fl8", "cw", "taxi", "bj", "fl8-map", "fle8-wide")
+                and c[1:4] == ("one_step", "tabular", "eps_greedy")]
+MATRIX_LAUNCHES = 2
+assert len(MATRIX) == 160 and len(MATRIX_FIXED) == 6
+
+
+def matrix_need(c):
+    """the conditions every matrix case of its kind meets (measured on the oracle).
+    Under UCB the lanes of CliffWalking and FrozenLake 8x8 start in one cell and pick
+    the same actions, so rows are covered by equal traces and episodes outlast the
+    window: those conditions are asserted for eps-greedy."""
+    need = ()
+    if c[1] == "traces":
+        need += ("decayed_E", "grid_rounded")
+        if c[3] == "eps_greedy":
+            need += ("row_count_exceeds_nonzero", "E_ge_2", "cleared_then_revisited")
+    if c[4] == "expected_sarsa":
+        need += ("es_counts_moved_in_step",) if c[3] == "ucb" else ("es_eps_decayed_between_updates",)
+    return need
+
+
+def check_matrix_case(obj, p, c, ln, q_mode=None, info=None):
+    """the same on either side: obj is the oracle's Batch or the device's Agent of case c"""
+    auto = obj.q_repr()
+    assert (auto == "fixed40") == (c in MATRIX_FIXED)
+    if q_mode:
+        obj.set_q_mode(q_mode)
+        assert obj.q_repr() == q_mode
+    if mc.presets_ucb(c):
+        obj.set_ucb(*mc.ucb_preset(obj.S, obj.A))
+    (obj.set_record if hasattr(obj, "set_record") else obj.set_recording)(True)
+    met = replay_and_check(obj, p, lambda: obj_run(obj), launches=MATRIX_LAUNCHES, ln=ln, info=info)
+    assert_coverage(met, matrix_need(c))
+
+
+def oracle_ln(oracle):
+    log = oracle.lib().rlo_log
+    return lambda ts: [log(float(t)) for t in ts]
+
+
+@pytest.mark.parametrize("c", MATRIX, ids=mc.case_id)
+def test_oracle_matrix_case_equals_replay_model(oracle, c):
+    p = oracle.default_params(**mc.shared_kw(c))
+    check_matrix_case(oracle.Batch(p), p, c, oracle_ln(oracle))
+
+
+@pytest.mark.parametrize("c", MATRIX_FIXED, ids=mc.case_id)
+def test_oracle_matrix_case_forced_f64_equals_replay_model(oracle, c):
+    p = oracle.default_params(**mc.shared_kw(c))
+    check_matrix_case(oracle.Batch(p), p, c, oracle_ln(oracle), q_mode="f64")
+
+
+# edges the matrix lacks: id -> (params, conditions the case must meet)
+EDGE_COMMON = dict(sync_every=8, n_episodes_for_decay=40)
+CW_TRACES = dict(env="cliff_walking", agent="traces", algo="sarsa", group_size=64, n_lanes=200)
+EDGE_CASES = {
+    # gamma * lambda at and above 1: Ebound is the geometric sum over the longest episode
+    "cw-traces-gl-1": (dict(CW_TRACES, gamma=1.0, lambda_=1.0), ("E_ge_2", "grid_rounded")),
+    "cw-traces-gl-1.5": (dict(CW_TRACES, gamma=1.0, lambda_=1.5, max_steps=20), ("E_ge_2", "decayed_E")),
+    # lr 1e300 reaches +-inf and NaN within a few steps (tests/test_gpu_f64.py runs the
+    # same three pair-storage forms against the oracle)
+    "cw-traces-lr1e300": (dict(CW_TRACES, lr=1e300), ("nonfinite_zero_E", "merge_nonfinite")),
+    "taxi-traces-lr1e300": (dict(env="taxi", agent="traces", algo="qlearning", group_size=128, n_lanes=200, lr=1e300),
+                            ("nonfinite_zero_E", "merge_nonfinite")),
+    "bj-traces-double-lr1e300": (dict(env="blackjack", agent="traces", policy="double", algo="sarsa", group_size=256,
+                                      n_lanes=300, lr=1e300), ("nonfinite_zero_E", "merge_nonfinite")),
+    # fresh counters: the NaN regime of SURVEY F7 and the kernel's IEEE shortcuts
+    "taxi-ucb-es-fresh": (dict(env="taxi", selector="ucb", algo="expected_sarsa", group_size=128, n_lanes=200),
+                          ("es_nan_shortcut", "es_counts_moved_in_step", "merge_nonfinite")),
+    # one group of 512: more than 64 (lane, state) pairs on a row
+    "cw-traces-G512": (dict(CW_TRACES, algo="qlearning", group_size=512, n_lanes=600),
+                       ("n_ge_64", "row_count_exceeds_nonzero", "decayed_E")),
+    "one-lane-traces": (dict(CW_TRACES, group_size=2, n_lanes=1), ("decayed_E",)),
+}
+
+
+def check_edge_case(obj, p, name, ln, info=None):
+    (obj.set_record if hasattr(obj, "set_record") else obj.set_recording)(True)
+    assert obj.q_repr() == "f64"
+    met = replay_and_check(obj, p, lambda: obj_run(obj), launches=MATRIX_LAUNCHES, ln=ln, info=info)
+    assert_coverage(met, EDGE_CASES[name][1])
+
+
+@pytest.mark.parametrize("name", list(EDGE_CASES))
+def test_oracle_edge_case_equals_replay_model(oracle, name):
+    p = oracle.default_params(**EDGE_COMMON, **EDGE_CASES[name][0])
+    check_edge_case(oracle.Batch(p), p, name, oracle_ln(oracle))
