@@ -103,10 +103,23 @@ sequence, not libm's.  `ln` is a callable int -> float supplied by the caller
 from the side under test; the tests check every value used against a 50-digit
 decimal logarithm (within 1 ulp), which makes it a checked scalar input.
 
+Records as the input, or predicted
+----------------------------------
+By itself this file takes (kind, s, a, s2, a2, r, term) from the records.
+tests/select_model.py closes the loop: its Predictor (replay_launch's
+`predictor`) produces every record of a group's step from the seed, the lanes'
+envs and the group's step-start snapshot (SnapshotView below), and the combine,
+the merge and the counters here then run on the predicted records.  What is
+pinned then: the stream and its mappings, the envs, the selections, the
+schedule, td, Q words, N, t and epsilon.  Record-driven replay and
+td_source="record" stay as they were.
+
 Outside the model
 -----------------
-Private mode (group_size 1) and the neural policy; the RNG, the envs and the
-selections themselves (records are the input).
+ln(t) (a checked input); the train() evaluate interleave (plain run() launches
+in RL_MODE_TRAIN only); private mode (group_size 1); the neural policy;
+populations.  Without a predictor also the RNG, the envs and the selections
+themselves (records are the input).
 """
 import math
 import struct
@@ -294,6 +307,45 @@ class LaneTrace:
         self.rows, self.last, self.taken = {}, set(), set()
 
 
+class SnapshotView:
+    """what a selection may read of its group at the start of a step: the group's
+    current values and raw words (Q_base where the group has not moved an entry),
+    the group's counters N / t as incremented by its earlier steps, ln(t) and the
+    lanes' epsilon.  The dicts are replay_launch's own: they move when the step's
+    updates are applied, after every selection of the step."""
+
+    def __init__(self, P, S, A, f64, base, base_val, raw, val, n_base, n_inc, eps, ln_used, ln):
+        self.P, self.S, self.A, self.f64 = P, S, A, f64
+        self._base, self._base_val, self._raw, self._val = base, base_val, raw, val
+        self._n_base, self._n_inc, self.eps, self._ln_used, self._ln = n_base, n_inc, eps, ln_used, ln
+        self.t = 0
+
+    def row(self, tbl, s):
+        i0 = (tbl * self.S + s) * self.A
+        return [self._val[i] if i in self._val else self._base_val[i] for i in range(i0, i0 + self.A)]
+
+    def raw_row(self, tbl, s):
+        i0 = (tbl * self.S + s) * self.A
+        return [self._raw[i] if i in self._raw else self._base[i] for i in range(i0, i0 + self.A)]
+
+    def counts(self, s):
+        return [self._n_base[s * self.A + i] + self._n_inc.get(s * self.A + i, 0) for i in range(self.A)]
+
+    def ln_t(self):
+        if self.t not in self._ln_used:
+            self._ln_used[self.t] = float(self._ln(self.t))
+        return self._ln_used[self.t]
+
+    def moved(self, s):
+        """whether the group holds an entry of row s (either table) that differs from Q_base's"""
+        for tbl in range(self.P):
+            i0 = (tbl * self.S + s) * self.A
+            for i in range(i0, i0 + self.A):
+                if i in self._raw and self._raw[i] != self._base[i]:
+                    return True
+        return False
+
+
 # ---------------------------------------------------------------- the model
 def _first_max(row):
     m = row[0]
@@ -341,7 +393,7 @@ def expected_ucb(row2, counts, lnt, c):
 def replay_launch(q_base, n_base, t_base, records, *, G, P, S, A, lr, gamma, algo, repr,
                   merge_groups=0, ucb=False, flags=None, agent="one_step", td_source="model",
                   eps=None, eps_decay=0.0, eps_final=0.0, decay_kind=0, ucb_c=0.5, ln=None,
-                  lam=0.0, max_steps=0, blackjack=False, traces=None, last_eps=None):
+                  lam=0.0, max_steps=0, blackjack=False, traces=None, last_eps=None, predictor=None):
     """Predict Q_base's raw words, N / t and the lanes' epsilon after one launch.
 
     q_base: P*S*A int64 raw words ([P][S][A] order); n_base: S*A counts; t_base: int;
@@ -357,6 +409,10 @@ def replay_launch(q_base, n_base, t_base, records, *, G, P, S, A, lr, gamma, alg
     flags / traces: per-lane double-policy flag and LaneTrace before the launch
     (None: the state at creation); last_eps: the epsilon of every lane's latest
     expected-SARSA update (None where it made none; coverage only).
+    predictor: None (records are the input), or tests/select_model.py's Predictor.
+    Then `records` is a [K][n_lanes] grid of None that the predictor fills group by
+    group and step by step from the group's step-start snapshot (a SnapshotView),
+    and every STEP record receives the td computed here.
     """
     if agent not in ("one_step", "traces"):
         raise ValueError(f"unknown agent {agent!r}")
@@ -366,6 +422,8 @@ def replay_launch(q_base, n_base, t_base, records, *, G, P, S, A, lr, gamma, alg
         raise ValueError(f"unknown representation {repr!r}")
     if td_source not in ("model", "record"):
         raise ValueError(f"unknown td_source {td_source!r}")
+    if predictor is not None and td_source != "model":
+        raise ValueError("predicted records carry no td: a predictor needs td_source=\"model\"")
     if P not in (1, 2) or G < 2 or G > 1024:
         raise ValueError("shared mode: P in {1, 2}, 2 <= group_size <= 1024")
     if repr == "fixed40" and (P != 1 or agent != "one_step"):
@@ -420,7 +478,13 @@ def replay_launch(q_base, n_base, t_base, records, *, G, P, S, A, lr, gamma, alg
             i = (tbl * S + s) * A + a
             return val[i] if i in val else base_val[i]
 
+        view = None
+        if predictor is not None:
+            view = SnapshotView(P, S, A, f64, base, base_val, raw, val, n_base, n_inc, eps, out.ln_used, ln)
         for k in range(K):
+            if predictor is not None:
+                view.t = int(t_base) + t_inc
+                predictor.fill(records[k], k, lane0, lane1, view)
             # every selection of the step moves the counters before any update reads them
             step_inc = set()
             if ucb:
@@ -447,7 +511,8 @@ def replay_launch(q_base, n_base, t_base, records, *, G, P, S, A, lr, gamma, alg
                 if int(rec["mode"]) != MODE_TRAIN or kind not in (KIND_STEP, KIND_RESET_STEP):
                     continue
                 s, a, s2, a2 = int(rec["s"]), int(rec["a"]), int(rec["s2"]), int(rec["a2"])
-                r, td_rec = float(rec["r"]), float(rec["td"])
+                r = float(rec["r"])
+                td_rec = float(rec["td"]) if predictor is None else None
                 vt, ut = ((0, 1) if flags[j] else (1, 0)) if P == 2 else (0, 0)
                 if td_source == "record":
                     td = td_rec
@@ -473,7 +538,9 @@ def replay_launch(q_base, n_base, t_base, records, *, G, P, S, A, lr, gamma, alg
                     if es and not all(_finite(v) for v in row2):
                         out.seen.add("es_nan_shortcut")
                     td = r + gamma * nxt - V(vt, s, a)
-                    if not _same_f64(td, td_rec):
+                    if predictor is not None:
+                        rec["td"] = td
+                    elif not _same_f64(td, td_rec):
                         out.td_mismatches.append((g, k, j, td, td_rec))
                 if not tr:
                     contrib.setdefault((ut * S + s) * A + a, []).append(lr * td)
@@ -559,6 +626,8 @@ def replay_launch(q_base, n_base, t_base, records, *, G, P, S, A, lr, gamma, alg
                     val[i] = float(new) * 2.0 ** -FIX_SHIFT
                 out.steps.append(StepEvent(g, k, i, ds, kinds, e, move, old, new, contrib_E.get(i),
                                            td_big if tr else None, inexact))
+            if predictor is not None:
+                predictor.after_step(records[k], k, lane0, lane1, view)
         finals.append(raw)
         for i, c in n_inc.items():
             n_after[i] += c

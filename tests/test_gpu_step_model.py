@@ -10,6 +10,15 @@ one (expected SARSA's with the device's own log, rl_kat_log, checked against a
 records.  The traces and expected-SARSA combinations of the parity matrix and the
 edge cases run here as they do on the oracle.  No oracle call is made here, so a
 mistake shared by the oracle and the kernels cannot hide.
+
+The closed loop (tests/select_model.py) takes the records off the input side as
+well: every record field of every lane and step is predicted from the seed and
+the state before the launch, and the device's records, td, Q words, N, t and
+epsilon must equal the prediction.  All shared combinations of the parity matrix
+the device accepts run it (234 of 240; the registered-map and wide variants put
+fl_advance and fl_advance_wide on the path), the fixed-point ones once more in
+f64, the eps-greedy ones once more with the reset-and-step schedule, plus the
+units: Taxi deliveries, a group of 512 with rejected card halves, a single lane.
 """
 import ctypes as C
 
@@ -18,8 +27,9 @@ import pytest
 
 import matrix_cases as mc
 from test_step_model import (CASES, COMMON, EDGE_CASES, EDGE_COMMON, HEADROOM_CASE, MATRIX, MATRIX_FIXED, ONE_LANE,
-                             assert_coverage, check_edge_case, check_matrix_case, crafted_table,
-                             one_lane_plain_update, replay_and_check, setup_pair)
+                             SEL_EPS_GREEDY, SEL_FIXED, SEL_MATRIX, SEL_UNITS, assert_coverage, check_edge_case,
+                             check_matrix_case, check_selection_case, check_selection_unit, crafted_table,
+                             one_lane_plain_update, replay_and_check, sel_kw, setup_pair)
 
 pytestmark = pytest.mark.gpu
 
@@ -122,5 +132,52 @@ def test_device_edge_case_equals_replay_model(rl, name):
     dev = rl.Agent(p)
     try:
         check_edge_case(dev, p, name, device_ln(rl))
+    finally:
+        dev.close()
+
+
+# ---------------------------------------------------------------- the closed loop: records from the seed
+DEVICE_SEL = [c for c in SEL_MATRIX if not mc.shared_rejected(c)]
+assert len(DEVICE_SEL) == 234 and not any(mc.shared_rejected(c) for c in SEL_EPS_GREEDY + SEL_FIXED)
+
+
+@pytest.mark.parametrize("c", DEVICE_SEL, ids=mc.case_id)
+def test_device_records_equal_the_closed_loop(rl, c):
+    p = mc.device_params(rl, sel_kw(c), c)
+    dev = rl.Agent(p)
+    try:
+        check_selection_case(dev, p, c, device_ln(rl))
+    finally:
+        dev.close()
+
+
+@pytest.mark.parametrize("c", SEL_FIXED, ids=mc.case_id)
+def test_device_records_equal_the_closed_loop_forced_f64(rl, c):
+    p = mc.device_params(rl, sel_kw(c), c)
+    dev = rl.Agent(p)
+    try:
+        check_selection_case(dev, p, c, device_ln(rl), q_mode="f64")
+    finally:
+        dev.close()
+
+
+@pytest.mark.parametrize("c", SEL_EPS_GREEDY, ids=mc.case_id)
+def test_device_records_equal_the_closed_loop_reset_step(rl, c):
+    p = mc.device_params(rl, sel_kw(c), c)
+    dev = rl.Agent(p)
+    try:
+        st = check_selection_case(dev, p, c, device_ln(rl), reset_step=True)
+        assert st["resets"] >= p["n_lanes"]
+    finally:
+        dev.close()
+
+
+@pytest.mark.parametrize("name", list(SEL_UNITS))
+def test_device_unit_equals_the_closed_loop(rl, name):
+    c, over, _, _ = SEL_UNITS[name]
+    p = mc.device_params(rl, sel_kw(c, **over), c)
+    dev = rl.Agent(p)
+    try:
+        check_selection_unit(dev, p, name, device_ln(rl))
     finally:
         dev.close()

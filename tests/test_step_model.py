@@ -16,6 +16,11 @@ below pin the model itself word by word, and the live cases run every traces /
 expected-SARSA combination of the parity matrix plus the edges it lacks.
 Measured on the CPU: the slowest live case (Taxi, traces, double, UCB) takes
 0.7 s, almost all of it the model.
+
+The last sections close the loop (tests/select_model.py): the records themselves
+are predicted from the seed, on all 240 shared combinations of the matrix, with
+liveness conditions asserted per case, five negative controls and seven
+hand-worked tests; the slowest of those cases takes 0.5 s.
 """
 import decimal
 import math
@@ -667,3 +672,487 @@ def check_edge_case(obj, p, name, ln, info=None):
 def test_oracle_edge_case_equals_replay_model(oracle, name):
     p = oracle.default_params(**EDGE_COMMON, **EDGE_CASES[name][0])
     check_edge_case(oracle.Batch(p), p, name, oracle_ln(oracle))
+
+
+# ---------------------------------------------------------------- the closed loop: records from the seed
+# tests/select_model.py predicts every record of a launch from the seed and the state
+# before it; the replay above then runs on the predicted records.  All 240 shared
+# combinations of the parity matrix at its geometry (130 lanes in groups of 64, 64 and
+# 2, K 8), 2 launches from creation, with inputs chosen so that the selection
+# arithmetic is live (asserted per case by assert_selection_live, on the model's own
+# bookkeeping):
+#   - eps0 0.5 and a linear decay of 0.5 / (0.5 * 16) = 0.0625 per terminated episode:
+#     both branches of the eps test occur from the first step, the lanes' epsilons
+#     differ after their first episodes and Blackjack's reach the eps == 0 shortcut;
+#   - max_steps 5: every lane that survives truncates at its 7th synchronous step, inside
+#     the 16.  Two kinds of variant cannot end an episode in the env itself under that:
+#     on the deterministic 8x8 map the nearest hole (cell 19) is exactly 5 moves from the
+#     start, and a Taxi delivery takes a pickup, at least 4 moves and the drop-off.  They
+#     get inputs of their own, so that every case has both a terminal step of its env
+#     and a truncation:
+#       deterministic 8x8 (fl8, fl8-map, fle8-wide): max_steps 7 (truncation at the 9th
+#         step), the start table holds 1/2 in both tables at LAKE_STEER, the five
+#         (cell, action) pairs of the path 0 -> 8 -> 16 -> 17 -> 18 -> hole 19, and the UCB
+#         counters of those five rows are 1 in every action.  Greedy selections follow
+#         the path (1/2 > 3/8); under UCB, where a group's lanes move in lockstep, the
+#         first episode falls into the hole at its 5th move, the 64 increments then take
+#         the steered action's bonus from 1.46 to 0.18 and the second episode leaves the
+#         path and is truncated;
+#       Taxi: max_steps 13 (truncation at the 15th step) and a start table of twice the
+#         undiscounted optimal action values (integers; taxi_optimal_table) plus the
+#         {0, 1/8, 1/4, 3/8} draw: the optimal actions stay ahead by more than the draw and
+#         the UCB bonuses can reorder, equal optimal actions tie where their draws do, and
+#         lanes that start within reach deliver (+20) while the others are truncated;
+SEL_LAUNCHES = 2
+SEL_VALUES = (0.0, 0.125, 0.25, 0.375)
+SEL_COUNTS = (1, 4, 9)
+SEL_MATRIX = mc.combos()
+SEL_EPS_GREEDY = [c for c in SEL_MATRIX if c[3] == "eps_greedy"]
+# AUTO holds these in the fixed point (one-step agent, single table: the range proof
+# covers SARSA, Q-learning and expected SARSA over eps-greedy, and SARSA / Q-learning
+# whatever selected the actions); they run once more forced to f64
+SEL_FIXED = [c for c in SEL_MATRIX if c[0] in ("fl8", "cw", "taxi", "bj", "fl8-map", "fle8-wide")
+             and c[1:3] == ("one_step", "tabular") and (c[3] == "eps_greedy" or c[4] != "expected_sarsa")]
+assert len(SEL_MATRIX) == 240 and len(SEL_EPS_GREEDY) == 120
+# combinations that cannot meet a liveness condition: name -> reason (cap: 5 % of 240)
+SEL_LEFT_OUT = {}
+assert len(SEL_LEFT_OUT) <= 12
+
+
+LAKE_STEER = ((0, 1), (8, 1), (16, 2), (17, 2), (18, 2))      # down, down, right, right, right: into cell 19
+
+
+def lake_det8(kw):
+    return kw["env"].startswith("frozen_lake") and bool(kw["map8x8"]) and not kw["slippery"]
+
+
+def sel_kw(c, **over):
+    kw = dict(mc.shared_kw(c), eps0=0.5, n_episodes_for_decay=16)
+    kw["max_steps"] = 13 if kw["env"] == "taxi" else (7 if lake_det8(kw) else 5)
+    kw.update(over)
+    return kw
+
+
+def sel_table(P, S, A, kw, seed=11):
+    q = np.random.RandomState(seed).choice(SEL_VALUES, size=(P, S, A))
+    if kw["env"] == "taxi":
+        q += 2.0 * taxi_optimal_table()
+    elif lake_det8(kw):
+        for s, a in LAKE_STEER:
+            q[:, s, a] = 0.5
+    return q
+
+
+def sel_counters(S, A, kw, seed=20):
+    """half the rows hold one count in every action (the scores tie where the values
+    do), the others a count per entry"""
+    rs = np.random.RandomState(seed)
+    counts = rs.choice(SEL_COUNTS, size=(S, A))
+    flat = rs.rand(S) < 0.5
+    counts[flat, :] = rs.choice(SEL_COUNTS, size=(S, 1))[flat, :]
+    if lake_det8(kw):
+        for s, _ in LAKE_STEER:
+            counts[s, :] = 1
+    return counts.astype(np.uint64), np.uint64(5000)
+
+
+def sel_prepare(obj, kw, q_mode=None, reset_step=False):
+    obj.set_q(sel_table(obj.P, obj.S, obj.A, kw))
+    if q_mode:
+        obj.set_q_mode(q_mode)
+    if kw["selector"] == "ucb":
+        obj.set_ucb(*sel_counters(obj.S, obj.A, kw))
+    if reset_step:
+        obj.set_reset_step(True)
+    (obj.set_record if hasattr(obj, "set_record") else obj.set_recording)(True)
+
+
+def sel_predictor(p, kw, reset_step=False, mutation=None):
+    """kw: the case's own parameters (a device case's p carries a registered map's id
+    in map8x8; the model runs the built-in rows the copy was made of)"""
+    import select_model as selm
+    return selm.Predictor(env=kw["env"], n_lanes=p["n_lanes"], seed=p["seed"], lane_offset=p["lane_offset"],
+                          map8x8=kw.get("map8x8", 0), slippery=kw.get("slippery", 0), max_steps=p["max_steps"],
+                          ucb=kw["selector"] == "ucb", ucb_c=p["ucb_c"], reset_step=reset_step,
+                          eps_decay=p["eps_decay"], eps_final=p["eps_final"], decay_kind=p["decay_kind"],
+                          mutation=mutation)
+
+
+def sel_launch_kw(obj, p):
+    kw = model_kw(obj, p)
+    for k in ("ucb", "ucb_c", "eps_decay", "eps_final", "decay_kind"):       # the predictor's
+        del kw[k]
+    return kw
+
+
+def sel_ln_table(p, t0, ln):
+    ts = list(range(int(t0), int(t0) + p["sync_every"] * min(p["group_size"], p["n_lanes"]) + 1))
+    return dict(zip(ts, (float(v) for v in ln(ts))))
+
+
+def predict_and_check(obj, p, kw, ln, *, launches=SEL_LAUNCHES, reset_step=False, keep=None):
+    """obj (an oracle Batch or a device Agent, prepared and recording) against the
+    closed loop: every record field, td, Q word, N, t and epsilon of every launch.
+    Returns the model's bookkeeping; keep (a list) receives every launch's inputs and
+    records for the negative controls."""
+    import select_model as selm
+    pr = sel_predictor(p, kw, reset_step)
+    assert (pr.S, pr.A) == (obj.S, obj.A)
+    lkw = sel_launch_kw(obj, p)
+    flags = traces = last_eps = None
+    eps = np.asarray(obj.epsilon(), np.float64).tolist()
+    for li in range(launches):
+        q0 = obj.q_raw().reshape(-1).tolist()
+        n0, t0 = obj.ucb()
+        n0 = np.asarray(n0).reshape(-1).tolist()
+        obj_run(obj)
+        recs = _records_as_dicts(obj.records())
+        assert len(recs) == p["sync_every"] and len(recs[0]) == p["n_lanes"]
+        table = sel_ln_table(p, t0, ln) if pr.ucb else {}
+        if keep is not None:
+            keep.append((q0, n0, int(t0), recs, table, obj.q_repr()))
+        rep, _, bad = selm.predict_launch(pr, q0, n0, int(t0), p["sync_every"], recorded=recs, repr=obj.q_repr(),
+                                          flags=flags, eps=eps, traces=traces, last_eps=last_eps,
+                                          ln=table.__getitem__, **lkw)
+        flags, eps, traces, last_eps = rep.flags, rep.eps, rep.traces, rep.last_eps
+        assert_ln_within_1ulp(rep.ln_used)
+        assert not bad, f"launch {li}: {len(bad)} record fields differ (step, lane, field, model, got): {bad[:6]}"
+        nbad, diffs = _first_diffs(obj.q_raw().reshape(-1).tolist(), rep.words)
+        assert nbad == 0, f"launch {li}: {nbad} Q words differ (entry, got, model): {diffs}"
+        n1, t1 = obj.ucb()
+        assert np.asarray(n1).reshape(-1).tolist() == rep.n and int(t1) == rep.t, f"launch {li}: UCB counters"
+        got_eps = np.asarray(obj.epsilon(), np.float64)
+        assert got_eps.view(np.uint64).tolist() == [sm.f64_bits(x) for x in rep.eps], f"launch {li}: epsilon"
+    return pr.totals()
+
+
+def assert_selection_live(st, kw, name=""):
+    """the issue's per-case conditions on the model's bookkeeping"""
+    if name in SEL_LEFT_OUT:
+        return
+    if kw["selector"] == "eps_greedy":
+        n = st["explore"] + st["greedy"] + st["eps_zero"]          # every selection is one of the three
+        assert st["explore"] >= 0.1 * n and st["greedy"] + st["eps_zero"] >= 0.1 * n, st
+    assert st["winner_ge_1"] >= 20 and st["ties_broken"] >= 5 and st["after_row_moved"] >= 1, st
+    assert st["resets"] >= 1 and st["terminal"] >= 1, st           # the env's own terminal steps
+    if kw["env"] != "blackjack":                                    # Blackjack has no max_steps
+        assert st["truncated"] >= 1, st
+
+
+def check_selection_case(obj, p, c, ln, q_mode=None, reset_step=False):
+    kw = sel_kw(c)
+    sel_prepare(obj, kw, q_mode, reset_step)
+    if q_mode:
+        assert obj.q_repr() == q_mode
+    else:
+        assert (obj.q_repr() == "fixed40") == (c in SEL_FIXED), obj.q_repr()
+    st = predict_and_check(obj, p, kw, ln, reset_step=reset_step)
+    assert_selection_live(st, kw, mc.case_id(c))
+    return st
+
+
+@pytest.mark.parametrize("c", SEL_MATRIX, ids=mc.case_id)
+def test_oracle_records_equal_the_closed_loop(oracle, c):
+    """Blackjack double-UCB runs here too (the device rejects it)"""
+    p = oracle.default_params(**sel_kw(c))
+    check_selection_case(oracle.Batch(p), p, c, oracle_ln(oracle))
+
+
+@pytest.mark.parametrize("c", SEL_FIXED, ids=mc.case_id)
+def test_oracle_records_equal_the_closed_loop_forced_f64(oracle, c):
+    p = oracle.default_params(**sel_kw(c))
+    check_selection_case(oracle.Batch(p), p, c, oracle_ln(oracle), q_mode="f64")
+
+
+@pytest.mark.parametrize("c", SEL_EPS_GREEDY, ids=mc.case_id)
+def test_oracle_records_equal_the_closed_loop_reset_step(oracle, c):
+    p = oracle.default_params(**sel_kw(c))
+    st = check_selection_case(oracle.Batch(p), p, c, oracle_ln(oracle), reset_step=True)
+    assert st["resets"] >= p["n_lanes"]
+
+
+# units beside the matrix: name -> (combination, parameters over sel_kw's, options,
+# minima of the model's bookkeeping the unit is there for).
+#   taxi-delivers-*: the start table is Taxi's undiscounted optimal action values
+#     (integers, exact in both representations; value iteration over the model's own
+#     table), max_steps 100 and eps0 0.125: greedy lanes deliver within the 16 steps
+#     (the env's own terminal step, +20), under either selector (UCB from a flat count
+#     of 9: the bonuses differ by less than the values' unit gaps);
+#   bj-G512-rejects: one group of 512 and a ragged one of 388; 6 of 65536 halves are
+#     rejected, about 3 over a 130-lane case and about 20 over this one;
+#   one-lane: a single lane in a group of its own;
+#   lane-offset: another seed and a lane offset.
+SEL_UNITS = {
+    "taxi-delivers-eps": (("taxi", "one_step", "tabular", "eps_greedy", "qlearning"),
+                          dict(max_steps=100, eps0=0.125), dict(table="taxi_optimal"), dict(terminal=20)),
+    "taxi-delivers-ucb": (("taxi", "one_step", "tabular", "ucb", "sarsa"),
+                          dict(max_steps=100), dict(table="taxi_optimal", counts=9), dict(terminal=20)),
+    "bj-G512-rejects": (("bj", "one_step", "tabular", "eps_greedy", "qlearning"),
+                        dict(n_lanes=900, group_size=512), {}, dict(rejected_halves=1, terminal=900)),
+    "one-lane": (("fl4-slip", "traces", "double", "eps_greedy", "expected_sarsa"),
+                 dict(n_lanes=1, group_size=2), {}, dict(resets=2)),
+    # the streams are keyed by the global lane id: lane_offset + lane
+    "lane-offset": (("fle8-slip", "one_step", "tabular", "eps_greedy", "sarsa"),
+                    dict(lane_offset=123457, seed=99), {}, dict(explore=200, terminal=1)),
+}
+
+
+def taxi_optimal_table():
+    import select_model as selm
+    obs, _ = selm.taxi_tables()
+    v = [0.0] * 500
+    for _ in range(40):                       # no state is more than 17 steps from its delivery
+        q = [[r + (0.0 if term else v[s2]) for s2, r, term in row] for row in obs]
+        v = [max(row) for row in q]
+    return np.asarray(q, np.float64).reshape(1, 500, 6)
+
+
+def check_selection_unit(obj, p, name, ln):
+    c, over, opt, need = SEL_UNITS[name]
+    kw = sel_kw(c, **over)
+    sel_prepare(obj, kw)
+    if opt.get("table") == "taxi_optimal":
+        obj.set_q(taxi_optimal_table())
+    if opt.get("counts"):
+        obj.set_ucb(np.full((obj.S, obj.A), opt["counts"], np.uint64), np.uint64(5000))
+    st = predict_and_check(obj, p, kw, ln)
+    short = {k: (st[k], m) for k, m in need.items() if st[k] < m}
+    assert not short, f"the unit no longer meets (got, needed): {short}"
+
+
+@pytest.mark.parametrize("name", list(SEL_UNITS))
+def test_oracle_unit_equals_the_closed_loop(oracle, name):
+    c, over, _, _ = SEL_UNITS[name]
+    p = oracle.default_params(**sel_kw(c, **over))
+    check_selection_unit(oracle.Batch(p), p, name, oracle_ln(oracle))
+
+
+# negative controls: a model with one rule switched must disagree with the oracle's
+# records on a live case (mutation -> the cases it is tried on; every one must report)
+SEL_MUTANTS = {
+    "tie_last": [("cw", "one_step", "tabular", "eps_greedy", "qlearning"),
+                 ("taxi", "traces", "double", "ucb", "sarsa")],
+    "end_snapshot": [("fl8-slip-wide", "one_step", "tabular", "eps_greedy", "qlearning"),
+                     ("taxi", "one_step", "double", "eps_greedy", "expected_sarsa")],
+    "alpha_only": [("bj", "one_step", "double", "eps_greedy", "sarsa"),
+                   ("fl4-slip", "traces", "double", "ucb", "qlearning")],
+    "counters_incremented": [("taxi", "one_step", "tabular", "ucb", "sarsa"),
+                             ("bj", "one_step", "double", "ucb", "expected_sarsa")],
+    "eps_post_decay": [("bj", "one_step", "tabular", "eps_greedy", "qlearning"),
+                       ("cw", "traces", "tabular", "eps_greedy", "sarsa")],
+}
+
+
+@pytest.mark.parametrize("mutation", list(SEL_MUTANTS))
+def test_closed_loop_mutation_is_detected(oracle, mutation):
+    import select_model as selm
+    assert mutation in selm.MUTATIONS and set(SEL_MUTANTS) == set(selm.MUTATIONS)
+    for c in SEL_MUTANTS[mutation]:
+        kw = sel_kw(c)
+        p = oracle.default_params(**kw)
+        ref = oracle.Batch(p)
+        sel_prepare(ref, kw)
+        keep = []
+        st = predict_and_check(ref, p, kw, oracle_ln(oracle), keep=keep)       # the true model agrees
+        assert_selection_live(st, kw, mc.case_id(c))
+        pr = sel_predictor(p, kw, mutation=mutation)
+        lkw = sel_launch_kw(ref, p)
+        flags = traces = last_eps = None
+        eps = [p["eps0"]] * p["n_lanes"]
+        found = []
+        for q0, n0, t0, recs, table, rp in keep:
+            rep, _, bad = selm.predict_launch(pr, q0, n0, t0, p["sync_every"], recorded=recs, repr=rp, flags=flags,
+                                              eps=eps, traces=traces, last_eps=last_eps,
+                                              ln=table.__getitem__, **lkw)
+            flags, eps, traces, last_eps = rep.flags, rep.eps, rep.traces, rep.last_eps
+            found += bad
+        assert found, f"{mutation} goes unnoticed on {mc.case_id(c)}: the case is too weak"
+
+
+# ---------------------------------------------------------------- hand-worked: the closed loop
+# no oracle, no library: CliffWalking (no draws; 0 LEFT, 1 DOWN, 2 RIGHT, 3 UP; start 36
+# in the bottom-left corner, where LEFT and DOWN stay in place), two identical lanes in
+# one group, epsilon 0 (greedy, no draw) unless said otherwise, lr 0.5, gamma 0.5
+class _Words:
+    """a stream that hands out the given u32 words"""
+
+    def __init__(self, *words):
+        self.words, self.rejected_halves = list(words), 0
+
+    def u32(self):
+        return self.words.pop(0)
+
+    def u64(self):
+        lo = self.u32()
+        return lo | (self.u32() << 32)
+
+    def uniform01(self):
+        return sm.f64_from_bits((self.u64() >> 12) | 0x3FF0000000000000) - 1.0
+
+
+def _cliff(rows, K, *, P=1, lanes=2, max_steps=100, ucb=False, n_rows=None, ln=None, mutation=None):
+    """rows: {(table, state): [4 values]} over a zero table; n_rows: {state: [4 counts]}"""
+    import select_model as selm
+    pr = selm.Predictor(env="cliff_walking", n_lanes=lanes, seed=1, max_steps=max_steps, ucb=ucb, ucb_c=1.0,
+                        mutation=mutation)
+    q = [0.0] * (P * 48 * 4)
+    for (tbl, s), vals in rows.items():
+        q[(tbl * 48 + s) * 4:(tbl * 48 + s) * 4 + 4] = vals
+    n0 = [0] * (48 * 4)
+    for s, vals in (n_rows or {}).items():
+        n0[s * 4:s * 4 + 4] = vals
+    rep, recs, _ = selm.predict_launch(pr, [sm.f64_word(v) for v in q], n0, 1, K, G=2, P=P, S=48, A=4, lr=0.5,
+                                       gamma=0.5, algo="qlearning", repr="f64", eps=[0.0] * lanes, ln=ln)
+    assert all(_fields(recs[k][0]) == _fields(recs[k][-1]) for k in range(K))      # identical lanes
+    return rep, [r[0] for r in recs], pr
+
+
+def _fields(rec, names=("kind", "s", "a", "s2", "a2", "r", "term")):
+    return tuple(rec[n] for n in names)
+
+
+def test_closed_loop_tie_at_1_and_3_takes_1_until_the_entry_moves():
+    """row 36 = [1/8, 3/8, 1/4, 3/8]: the maximum is at 1 and 3, the first wins.
+    k0 RESET: a = 1.  k1 DOWN stays at 36 (r -1); a2 reads the same snapshot: 1;
+    td = -1 + 0.5 * 3/8 - 3/8 = -1.1875 and Q[36][1] = 3/8 - 0.59375 = -0.21875 (two equal
+    contributions, their mean).  k2: the row is now [1/8, -0.21875, 1/4, 3/8], a2 = 3;
+    td = -1 + 0.1875 + 0.21875 = -0.59375.  k3 UP moves to 24 (zero row): a2 = 0."""
+    rep, recs, pr = _cliff({(0, 36): [0.125, 0.375, 0.25, 0.375]}, 4)
+    assert [_fields(r) for r in recs] == [(1, 36, 1, 0, 0, 0.0, 0), (2, 36, 1, 36, 1, -1.0, 0),
+                                          (2, 36, 1, 36, 3, -1.0, 0), (2, 36, 3, 24, 0, -1.0, 0)]
+    assert [r["td"] for r in recs] == [0.0, -1.1875, -0.59375, -1.0 + 0.5 * 0.0 - 0.375]
+    st = pr.totals()
+    # ties: k0, k1 and k3's zero row 24, for each lane; k2 reads row 36 after it moved
+    assert st["ties_broken"] == 2 * 3 and st["after_row_moved"] == 2 * 1
+    # the last maximum instead: a = 3 at the reset already
+    _, recs, _ = _cliff({(0, 36): [0.125, 0.375, 0.25, 0.375]}, 1, mutation="tie_last")
+    assert _fields(recs[0])[:3] == (1, 36, 3)
+    # reading the values after the step's updates: k1's a2 is 3 a step early
+    _, recs, _ = _cliff({(0, 36): [0.125, 0.375, 0.25, 0.375]}, 2, mutation="end_snapshot")
+    assert _fields(recs[1]) == (2, 36, 1, 36, 3, -1.0, 0)
+
+
+def test_closed_loop_nan_at_0_wins_and_nan_at_2_never_does():
+    import select_model as selm
+    nan = float("nan")
+    assert selm.argmax_first([nan, 5.0, 1.0, 7.0]) == (0, False)
+    assert selm.argmax_first([0.25, 0.125, nan, 0.375]) == (3, False)
+    assert selm.argmax_first([0.5, 0.125, nan, 0.375]) == (0, False)
+    # through a launch: NaN at LEFT keeps the lane in the corner, td and the entry go NaN
+    rep, recs, pr = _cliff({(0, 36): [nan, 5.0, 1.0, 7.0]}, 2)
+    assert _fields(recs[0]) == (1, 36, 0, 0, 0, 0.0, 0) and _fields(recs[1])[:5] == (2, 36, 0, 36, 0)
+    assert recs[1]["td"] != recs[1]["td"] and rep.words[36 * 4] == sm.QNAN_BITS
+    # NaN at RIGHT: UP (7.0) wins; a UCB score of NaN at 0 wins the same way
+    _, recs, _ = _cliff({(0, 36): [0.25, 5.0, nan, 7.0]}, 1)
+    assert _fields(recs[0])[:3] == (1, 36, 3)
+    assert selm.argmax_first(selm.ucb_scores([nan, 9.0], [1, 1], 4.0, 1.0)) == (0, False)
+
+
+def test_closed_loop_double_policy_selects_on_the_average():
+    """alpha[36] = [0, 0, 0, 3/8], beta[36] = [1/2, 0, 0, 0]: (alpha + beta) / 2 =
+    [1/4, 0, 0, 3/16] picks LEFT; alpha alone picks UP"""
+    rows = {(0, 36): [0.0, 0.0, 0.0, 0.375], (1, 36): [0.5, 0.0, 0.0, 0.0]}
+    _, recs, _ = _cliff(rows, 2, P=2)
+    assert _fields(recs[0]) == (1, 36, 0, 0, 0, 0.0, 0) and _fields(recs[1]) == (2, 36, 0, 36, 0, -1.0, 0)
+    # the update reads alpha (flag true): td = -1 + 0.5 * 3/8 - 0 = -0.8125
+    assert recs[1]["td"] == -0.8125
+    _, recs, _ = _cliff(rows, 1, P=2, mutation="alpha_only")
+    assert _fields(recs[0])[:3] == (1, 36, 3)
+
+
+def test_closed_loop_ucb_reads_the_step_start_counters():
+    """zero values, c = 1, ln(t) given as 4: N[36] = [1, 1, 4, 4] scores [2, 2, 1, 1]: both
+    lanes of the group take LEFT (the first maximum) at the reset.  Had lane 1 read
+    lane 0's increment, N = [2, 1, 4, 4] would score [1.41, 2, 1, 1]: DOWN.  After the
+    step N[36][0] = 3 and t = 3; at k1 both read [3, 1, 4, 4] -> [1.15, 2, 1, 1]: DOWN."""
+    import select_model as selm
+    rep, recs, pr = _cliff({}, 2, ucb=True, n_rows={36: [1, 1, 4, 4]}, ln=lambda t: 4.0)
+    assert _fields(recs[0]) == (1, 36, 0, 0, 0, 0.0, 0) and _fields(recs[1]) == (2, 36, 0, 36, 1, -1.0, 0)
+    assert rep.n[36 * 4:36 * 4 + 4] == [3, 3, 4, 4] and rep.t == 5 and sorted(rep.ln_used) == [1, 3]
+    pr = selm.Predictor(env="cliff_walking", n_lanes=2, seed=1, ucb=True, ucb_c=1.0, mutation="counters_incremented")
+    n0 = [0] * 192
+    n0[144:148] = [1, 1, 4, 4]
+    _, recs, _ = selm.predict_launch(pr, [0] * 192, n0, 1, 1, G=2, P=1, S=48, A=4, lr=0.5, gamma=0.5,
+                                     algo="qlearning", repr="f64", eps=[0.0, 0.0], ln=lambda t: 4.0)
+    assert (recs[0][0]["a"], recs[0][1]["a"]) == (0, 1)
+
+
+def test_card_word_with_a_rejected_high_half():
+    """h = 6553: 6553 * 10 = 65530 > 65529 is rejected; the low half 0x8000 gives
+    1 + (327680 >> 16) = 6, from the same word.  h = 6552: 65520, card 1; 0xffff: card 10."""
+    import select_model as selm
+    assert selm.card_of_half(6553) == (1, True) and selm.card_of_half(6552) == (1, False)
+    assert selm.card_of_half(0x8000) == (6, False) and selm.card_of_half(0xFFFF) == (10, False)
+    assert sum(selm.card_of_half(h)[1] for h in range(1 << 16)) == 6
+    rng = _Words((6553 << 16) | 0x8000, 0xDEAD0000)
+    src = selm.CardSource(rng)
+    assert src.card() == 6 and rng.rejected_halves == 1 and rng.words == [0xDEAD0000]    # one word for the hit
+    # a deal whose first word's high half is rejected needs a third word: cards 6 | 1, 10 | 4, a half left over
+    rng = _Words((6553 << 16) | 0x8000, (0 << 16) | 0xFFFF, (0x6666 << 16) | 0x1234, 7)
+    env = selm.Blackjack.__new__(selm.Blackjack)
+    env.n_trunc = 0
+    assert env.reset(rng) == selm.bj_index(17, 10, True) and rng.words == [7]      # 6 + ace = 17, dealer shows 10
+    # a hit takes its own word: the half left over by the deal is gone
+    rng.words = [(0x4000 << 16) | 0, 8]
+    assert env.step(0, rng) == (selm.bj_index(20, 10, True), 0.0, False) and rng.words == [8]   # 0x4000: card 3, soft 20
+
+
+def test_taxi_reset_above_the_last_running_sum_is_cell_0():
+    """300 start probabilities of 1/300 sum to 0.9999999999999961 in order; uniform01's
+    largest value 1 - 2^-52 is above it, no running sum exceeds it and the all-false
+    argmax gives cell 0, which is no start state (passenger at its destination)"""
+    import select_model as selm
+    env = selm.Taxi(6)
+    acc = 0.0
+    for v in env.start:
+        acc += v
+    assert acc == 0.9999999999999961 and env.start[0] == 0.0 and sum(1 for v in env.start if v) == 300
+    assert env.reset(_Words(0xFFFFFFFF, 0xFFFFFFFF)) == 0
+    below = _Words(0, 0xFFFFFFFF - (1 << 12))             # u = 1 - 2^-20 - ..: below the last sum
+    assert below.uniform01() < acc
+    # the last start state: taxi (4, 4), passenger at 3, destination 2
+    assert env.reset(_Words(0, 0xFFFFFFFF - (1 << 12))) == ((4 * 5 + 4) * 5 + 3) * 4 + 2 == 494
+
+
+def test_closed_loop_truncates_on_the_step_after_max_steps():
+    """max_steps 2, UP preferred at 36 and 24: k0 RESET, k1 36 -> 24, k2 24 -> 12 (the
+    last allowed step), k3 is asked of an env at curr_step 2 = max_steps: (0, -100.0,
+    term) without moving, and the selection reads row 0; k4 RESET"""
+    rows = {(0, 36): [0.0, 0.0, 0.0, 1.0], (0, 24): [0.0, 0.0, 0.0, 1.0], (0, 0): [0.0, 0.0, 2.0, 0.0]}
+    rep, recs, pr = _cliff(rows, 5, max_steps=2)
+    assert [_fields(r) for r in recs] == [(1, 36, 3, 0, 0, 0.0, 0), (2, 36, 3, 24, 3, -1.0, 0),
+                                          (2, 24, 3, 12, 0, -1.0, 0), (2, 12, 0, 0, 2, -100.0, 1),
+                                          (1, 36, 3, 0, 0, 0.0, 0)]
+    assert recs[3]["td"] == -100.0 + 0.5 * 2.0 - 0.0
+    st = pr.totals()
+    assert st["truncated"] == 2 and st["terminal"] == 0 and st["resets"] == 4
+
+
+def test_closed_loop_model_imports_neither_oracle_nor_library():
+    import ast
+    import select_model as selm
+    names = set()
+    for node in ast.walk(ast.parse(open(selm.__file__).read())):
+        if isinstance(node, ast.Import):
+            names |= {a.name.split(".")[0] for a in node.names}
+        elif isinstance(node, ast.ImportFrom):
+            names.add((node.module or "").split(".")[0])
+    assert names == {"golden", "maps_model", "step_model"}, names
+
+
+def test_closed_loop_tables_equal_the_fixture():
+    """the Taxi and CliffWalking tables restated in select_model against
+    tests/golden/tables.json (an independent restatement of its own)"""
+    import json
+    import os
+    import select_model as selm
+    tables = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "tables.json")))
+    obs, start = selm.taxi_tables()
+    for name, obs, start in (("taxi", obs, start),
+                             ("cliff_walking", selm.CliffWalking(100).obs, [float(i == 36) for i in range(48)])):
+        t = tables[name]
+        assert start == t["start"]
+        for s, row in enumerate(obs):
+            for a, (s2, r, term) in enumerate(row):
+                assert (t["prob"][s][a][0], t["next"][s][a][0], t["reward"][s][a][0], bool(t["term"][s][a][0])) == \
+                       (1.0, s2, r, term), (name, s, a)
