@@ -1,8 +1,8 @@
-// rl_host.cpp — host runtime behind include/rl.h: env table construction,
-// device memory layout, launch sequencing, the group merge, recording,
-// timing.  Everything compute-bearing runs in the gfx950 kernels; this file
-// only allocates, copies and launches.  There is no CPU fallback: without a
-// HIP device every compute entry point returns RL_E_HIP.
+// rl_host.cpp — host runtime behind include/rl.h: device memory layout, launch
+// sequencing, the group merge, recording, timing (the env tables it uploads are
+// built in rl_host_env.cpp).  Everything compute-bearing runs in the gfx950
+// kernels; this file only allocates, copies and launches.  There is no CPU
+// fallback: without a HIP device every compute entry point returns RL_E_HIP.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -12,23 +12,21 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
-#include <mutex>
-#include <string>
-#include <vector>
+#include <memory>
+#include <type_traits>
 
-#include "rl_kparams.h"
-#include "rl_taxi.h"
+#include "rl_host.h"
 
 using namespace rlamd;
 
-namespace {
-
-thread_local std::string g_err;
+static thread_local std::string g_err;
 
 int fail(int code, const std::string &msg) {
     g_err = msg;
     return code;
 }
+
+namespace {
 
 #define HIPC(expr)                                                                                 \
     do {                                                                                           \
@@ -38,345 +36,6 @@ int fail(int code, const std::string &msg) {
                         std::string(#expr) + ": " + hipGetErrorString(e_));                        \
     } while (0)
 
-// ------------------------------------------------------------------ env tables
-// The product's own construction of the reference envs (an independent
-// restatement from the oracle's and from tests/golden/make_tables.py).
-struct EnvHost {
-    int kind = 0;
-    uint32_t S = 0, A = 0, max_steps = 0;
-    std::vector<uint32_t> trans;  // packed, see rl_device.h EnvDev<>
-    std::vector<double> start;    // initial-state distribution
-    std::vector<double> cdf;      // running sum of `start` (categorical_sample, utils.rs:33-43)
-    double th1 = 0, th2 = 0, th3 = 0, trunc_reward = 0;
-    int32_t fixed_start = -1;     // categorical_sample over `cdf` is constant (single start state)
-    int32_t slippery = 0;         // FrozenLake with stochastic rows
-    std::vector<std::string> map;   // FrozenLake / FrozenLakeEdited grid (nrow x ncol); empty otherwise
-    int nrow = 0, ncol = 0;
-    int kenv = 0;                 // kernel-side env id (rl_kparams.h): kind, or ENV_FL_MAP / ENV_FLE_MAP
-    // registered maps with two or more 'S' cells: the start list the device searches,
-    // [n_list f64 running sums][n_list u32 cells] packed in f64 words (rl_kparams.h)
-    std::vector<double> start_list;
-    uint32_t n_list = 0;
-    // what the device reads as KParams::start_cdf / n_start
-    const std::vector<double> &dev_cdf() const { return env_map_start(kenv) ? start_list : cdf; }
-    uint32_t dev_n_start() const { return env_map_start(kenv) ? n_list : (uint32_t)cdf.size(); }
-};
-
-const char *const kFL4[] = {"SFFF", "FHFH", "FFFH", "HFFG"};                     // frozen_lake.rs:23
-const char *const kFL8[] = {"SFFFFFFF", "FFFFFFFF", "FFFHFFFF", "FFFFFHFF",       // frozen_lake.rs:25-28
-                            "FFFHFFFF", "FHHFFFHF", "FHFFHFHF", "FFFHFFFG"};
-const char *const kTaxiMap[] = {"+---------+", "|R: | : :G|", "| : | : : |", "| : : : : |",
-                                "| | : | : |", "|Y| : |B: |", "+---------+"};   // taxi.rs:22-30
-const int kTaxiLocs[4][2] = {{0, 0}, {0, 4}, {4, 0}, {4, 3}};                   // taxi.rs:31
-
-// utils::inc (src/utils.rs:53-76): 0 LEFT, 1 DOWN, 2 RIGHT, 3 UP, clamped
-void grid_move(int nrow, int ncol, int row, int col, int a, int &nr, int &nc) {
-    nr = row;
-    nc = col;
-    switch (a) {
-    case 0: nc = std::max(col - 1, 0); break;
-    case 1: nr = std::min(row + 1, nrow - 1); break;
-    case 2: nc = std::min(col + 1, ncol - 1); break;
-    case 3: nr = std::max(row - 1, 0); break;
-    default: break;
-    }
-}
-
-// FrozenLakeTerrain of a cell / of the neighbour in direction a, WALL off the
-// grid (src/env/frozen_lake_edited.rs get_obs :115-144, get_terrain :146-162)
-enum { kStart = 0, kWall = 1, kHole = 2, kGround = 3, kGoal = 4 };
-using Grid = std::vector<std::string>;
-int terrain(const Grid &map, int row, int col) {
-    const char ch = map[row][col];
-    return ch == 'S' ? kStart : ch == 'G' ? kGoal : ch == 'H' ? kHole : kGround;
-}
-int neighbour(const Grid &map, int nrow, int ncol, int row, int col, int a) {
-    switch (a) {
-    case 0: return col == 0 ? kWall : terrain(map, row, col - 1);
-    case 1: return row == nrow - 1 ? kWall : terrain(map, row + 1, col);
-    case 2: return col == ncol - 1 ? kWall : terrain(map, row, col + 1);
-    default: return row == 0 ? kWall : terrain(map, row - 1, col);
-    }
-}
-double terrain_value(int t) {   // FrozenLakeTerrain::value (frozen_lake_edited.rs:18-28)
-    return t == kHole ? -1.0 : t == kWall ? -0.5 : t == kStart ? 0.0 : t == kGround ? 0.5 : 1.0;
-}
-
-void finish_cdf(EnvHost &e) {
-    e.cdf.resize(e.start.size());
-    double b = 0.0;
-    for (size_t i = 0; i < e.start.size(); ++i) {
-        b += e.start[i];
-        e.cdf[i] = b;
-    }
-    // first i with cdf[i] > u for every u in [0, 1 - 2^-52]: fixed when all
-    // earlier sums are 0 and cdf[i] exceeds the largest uniform
-    e.fixed_start = -1;
-    for (size_t i = 0; i < e.cdf.size(); ++i) {
-        if (e.cdf[i] == 0.0) continue;
-        if (e.cdf[i] > 1.0 - 0x1p-52) e.fixed_start = (int32_t)i;
-        break;
-    }
-}
-
-// categorical_sample over the cdf (utils.rs:33-43): first i with cdf[i] > u, else 0
-uint32_t linear_sample(const std::vector<double> &cdf, double u) {
-    for (size_t i = 0; i < cdf.size(); ++i)
-        if (cdf[i] > u) return (uint32_t)i;
-    return 0;
-}
-// rl_taxi.h taxi_start (three probes) equals the linear search at every
-// boundary: each c_k and its neighbours, and the u around each k/300 where the
-// first probe moves (between boundaries both are constant).  Checked once.
-bool taxi_start_checked(const EnvHost &e) {
-    static int ok = -1;
-    if (ok >= 0) return ok == 1;
-    std::vector<double> us = {0.0, std::nextafter(1.0, 0.0)};
-    auto around = [&](double x) {
-        double lo = x, hi = x;
-        for (int i = 0; i < 8; ++i) { lo = std::nextafter(lo, 0.0); hi = std::nextafter(hi, 1.0); us.push_back(lo); us.push_back(hi); }
-        us.push_back(x);
-    };
-    for (double c : e.cdf) if (c > 0.0 && c < 1.0) around(c);
-    for (int j = 1; j < 300; ++j) around((double)j / 300.0);
-    ok = 1;
-    for (double u : us)
-        if (u >= 0.0 && u < 1.0 && taxi_start(e.cdf.data(), u) != linear_sample(e.cdf, u)) ok = 0;
-    return ok == 1;
-}
-
-// The process-wide map registry (rl.h rl_map_register): ids 0 / 1 are MAP_4X4 /
-// MAP_8X8, registered maps get 2, 3, ... in registration order and keep them for
-// the life of the process (nothing is ever removed, so an id is never reused).
-std::mutex g_map_mu;
-std::vector<Grid> &map_registry() {
-    static std::vector<Grid> maps = {Grid(kFL4, kFL4 + 4), Grid(kFL8, kFL8 + 8)};
-    return maps;
-}
-// the table format of every id (rl_map_register_wide: 1), parallel to the registry
-std::vector<uint8_t> &map_wide_flags() {
-    static std::vector<uint8_t> wide = {0, 0};
-    return wide;
-}
-bool map_lookup(int32_t id, Grid &out, bool *wide = nullptr) {
-    std::lock_guard<std::mutex> lock(g_map_mu);
-    const std::vector<Grid> &maps = map_registry();
-    if (id < 0 || (size_t)id >= maps.size()) return false;
-    out = maps[(size_t)id];
-    if (wide) *wide = map_wide_flags()[(size_t)id] != 0;
-    return true;
-}
-
-int build_env(const rl_env_config &c, EnvHost &e) {
-    e = EnvHost();
-    e.kind = c.kind;
-    e.kenv = c.kind;
-    e.max_steps = c.max_steps;
-    if (c.kind == RL_ENV_FROZEN_LAKE || c.kind == RL_ENV_FROZEN_LAKE_EDITED) {
-        const bool edited = c.kind == RL_ENV_FROZEN_LAKE_EDITED;
-        bool wide = false;
-        if (!map_lookup(c.map8x8, e.map, &wide))
-            return fail(RL_E_ARG, "unknown FrozenLake map id " + std::to_string(c.map8x8) +
-                                      " (0 = MAP_4X4, 1 = MAP_8X8, else an id from rl_map_register)");
-        const Grid &map = e.map;
-        // nrow x ncol, state = row * ncol + col (frozen_lake.rs:49-50, utils.rs:45-51)
-        const int nrow = (int)map.size(), ncol = (int)map[0].size();
-        e.nrow = nrow;
-        e.ncol = ncol;
-        // a registered map runs the kernels with the start variant (rl_kparams.h), a
-        // built-in one exactly the instantiations it always ran
-        if (c.map8x8 >= 2) e.kenv = edited ? ENV_FLE_MAP : ENV_FL_MAP;
-        if (wide) e.kenv = edited ? ENV_FLE_WIDE : ENV_FL_WIDE;   // rl_map_register_wide: the wide table
-        e.S = (uint32_t)(nrow * ncol);
-        e.A = 4;
-        e.trans.assign(e.S * 4, 0);
-        int n_start = 0;
-        for (int i = 0; i < nrow * ncol; ++i) n_start += map[i / ncol][i % ncol] == 'S';
-        e.start.assign(e.S, 0.0);   // frozen_lake.rs:52-65: 1/k on each of the k 'S' cells
-        for (int i = 0; i < nrow * ncol; ++i)
-            if (map[i / ncol][i % ncol] == 'S') e.start[i] = 1.0 / n_start;
-        // the deterministic outcome of direction a: next state, reward bit, terminated
-        auto judge = [&](int row, int col, int a, uint32_t &ns, bool &goal, bool &done) {
-            int nr, nc;
-            grid_move(nrow, ncol, row, col, a, nr, nc);
-            ns = (uint32_t)(nr * ncol + nc);
-            if (edited) {   // update_probability_matrix (frozen_lake_edited.rs:94-113): judged by
-                            // the terrain in the moved direction; 10.0 onto G, else -1.0
-                const int t = neighbour(map, nrow, ncol, row, col, a);
-                goal = t == kGoal;
-                done = t == kGoal || t == kHole;
-            } else {
-                const char ch = map[nr][nc];
-                goal = ch == 'G';
-                done = ch == 'G' || ch == 'H';
-            }
-        };
-        auto outcome = [&](int row, int col, int a) -> uint32_t {   // the packed byte (<= 64 cells)
-            uint32_t ns;
-            bool goal, done;
-            judge(row, col, a, ns, goal, done);
-            return ns | (goal ? 64u : 0u) | (done ? 128u : 0u);
-        };
-        for (int row = 0; !wide && row < nrow; ++row)
-            for (int col = 0; col < ncol; ++col)
-                for (int a = 0; a < 4; ++a) {
-                    const int s = row * ncol + col;
-                    const char ch = map[row][col];
-                    uint32_t w;
-                    if (ch == 'G' || ch == 'H') w = (uint32_t)s | 128u;              // (1.0, s, 0, true)
-                    else if (c.slippery)                                             // [(a-1)%4, a, (a+1)%4]
-                        w = outcome(row, col, (a + 3) & 3) | (outcome(row, col, a) << 8) |
-                            (outcome(row, col, (a + 1) & 3) << 16) | (1u << 24);
-                    else w = outcome(row, col, a);
-                    e.trans[s * 4 + a] = w;
-                }
-        if (wide) {
-            // the wide table (rl_kparams.h): one u16 per (s, direction), two per u32
-            // word; 'G' / 'H' cells (s, 0, terminated) in every direction
-            std::vector<uint16_t> t16((size_t)e.S * 4);
-            for (int row = 0; row < nrow; ++row)
-                for (int col = 0; col < ncol; ++col)
-                    for (int d = 0; d < 4; ++d) {
-                        const int s = row * ncol + col;
-                        const char ch = map[row][col];
-                        uint32_t ns;
-                        bool goal, done;
-                        judge(row, col, d, ns, goal, done);
-                        t16[(size_t)s * 4 + d] =
-                            (ch == 'G' || ch == 'H')
-                                ? (uint16_t)((uint32_t)s | WIDE_TERM)
-                                : (uint16_t)(ns | (goal ? WIDE_REWARD : 0u) | (done ? WIDE_TERM : 0u));
-                    }
-            e.trans.assign((size_t)e.S * 2, 0);
-            std::memcpy(e.trans.data(), t16.data(), t16.size() * 2);
-        }
-        e.slippery = c.slippery ? 1 : 0;
-        const double third = 1.0 / 3.0;
-        e.th1 = 0.0 + third;
-        e.th2 = e.th1 + third;
-        e.th3 = e.th2 + third;
-        e.trunc_reward = edited ? -1.0 : 0.0;   // frozen_lake.rs:119-122 / frozen_lake_edited.rs:227-231
-    } else if (c.kind == RL_ENV_CLIFF_WALKING) {
-        e.S = 48;
-        e.A = 4;
-        e.trans.assign(48 * 4, 0);
-        for (int row = 0; row < 4; ++row)
-            for (int col = 0; col < 12; ++col)
-                for (int a = 0; a < 4; ++a) {
-                    int nr, nc;
-                    grid_move(4, 12, row, col, a, nr, nc);
-                    const int ns = nr * 12 + nc;
-                    const bool cliff = ns >= 37 && ns <= 46, goal = ns == 47;  // cliff_walking.rs:9-11
-                    e.trans[(row * 12 + col) * 4 + a] =
-                        (uint32_t)ns | (cliff ? 64u : 0u) | ((cliff || goal) ? 128u : 0u);
-                }
-        e.start.assign(48, 0.0);
-        e.start[36] = 1.0;
-        e.trunc_reward = -100.0;
-    } else if (c.kind == RL_ENV_TAXI) {
-        e.S = 500;
-        e.A = 6;
-        e.trans.assign(500 * 6, 0);
-        e.start.assign(500, 0.0);
-        double total = 0.0;
-        auto enc = [](int r, int cc, int p, int d) { return ((r * 5 + cc) * 5 + p) * 4 + d; };
-        for (int r = 0; r < 5; ++r)
-            for (int cc = 0; cc < 5; ++cc)
-                for (int p = 0; p < 5; ++p)
-                    for (int d = 0; d < 4; ++d) {
-                        const int s = enc(r, cc, p, d);
-                        if (p < 4 && p != d) { e.start[s] += 1.0; total += 1.0; }
-                        for (int a = 0; a < 6; ++a) {
-                            int nr = r, nc = cc, np = p;
-                            uint32_t rcode = 0;  // -1
-                            bool term = false;
-                            if (a == 0) nr = std::min(r + 1, 4);
-                            else if (a == 1) nr = std::max(r - 1, 0);
-                            if (a == 2 && kTaxiMap[1 + r][2 * cc + 2] == ':') nc = std::min(cc + 1, 4);
-                            else if (a == 3 && kTaxiMap[1 + r][2 * cc] == ':') nc = std::max(cc - 1, 0);
-                            else if (a == 4) {
-                                if (p < 4 && r == kTaxiLocs[p][0] && cc == kTaxiLocs[p][1]) np = 4;
-                                else rcode = 1;  // -10
-                            } else if (a == 5) {
-                                if (r == kTaxiLocs[d][0] && cc == kTaxiLocs[d][1] && p == 4) {
-                                    np = d; term = true; rcode = 2;  // +20
-                                } else rcode = 1;
-                            }
-                            e.trans[s * 6 + a] = (uint32_t)enc(nr, nc, np, d) | (rcode << 9) | ((term ? 1u : 0u) << 11);
-                        }
-                    }
-        for (double &v : e.start) v /= total;   // taxi.rs:117-119
-        e.trunc_reward = 0.0;
-        // the kernels compute Taxi's transitions (rl_taxi.h taxi_word): all 3000 must
-        // equal the table built above
-        for (uint32_t i = 0; i < 500u * 6u; ++i)
-            if (taxi_word(i / 6u, i % 6u) != e.trans[i]) return fail(RL_E_STATE, "taxi_word differs from the table");
-    } else if (c.kind == RL_ENV_BLACKJACK) {
-        e.S = 32 * 32 * 2;   // dense (p_score <= 31, d_score <= 26 in 5 bits, p_ace): (p*32 + d)*2 + ace
-        e.A = 2;
-    } else {
-        return fail(RL_E_ARG, "unknown env kind");
-    }
-    if (!e.start.empty()) finish_cdf(e);
-    if (c.kind == RL_ENV_TAXI && !taxi_start_checked(e)) return fail(RL_E_STATE, "taxi_start differs from categorical_sample");
-    if (env_map_start(e.kenv)) {
-        // Env::reset on a registered map (DESIGN §2 "draws"): no 'S' is the all-false
-        // argmax's cell 0 (utils.rs:33-43), one 'S' a fixed start, neither drawn; two
-        // or more draw one uniform01 and search the list of the 'S' cells with their
-        // running sums — the sum changes nowhere else, so this is the full scan.
-        std::vector<uint32_t> cells;
-        for (uint32_t i = 0; i < e.S; ++i)
-            if (e.start[i] != 0.0) cells.push_back(i);
-        if (cells.empty()) e.fixed_start = 0;
-        else if (cells.size() == 1) e.fixed_start = (int32_t)cells[0];
-        else {
-            e.fixed_start = -1;
-            e.n_list = (uint32_t)cells.size();
-            e.start_list.assign(e.n_list + (e.n_list + 1) / 2, 0.0);
-            for (uint32_t j = 0; j < e.n_list; ++j) e.start_list[j] = e.cdf[cells[j]];
-            std::memcpy(e.start_list.data() + e.n_list, cells.data(), cells.size() * sizeof(uint32_t));
-            // the list against the full scan at every boundary and its neighbours
-            std::vector<double> us = {0.0, std::nextafter(1.0, 0.0)};
-            for (uint32_t j = 0; j < e.n_list; ++j)
-                for (double x : {e.start_list[j], std::nextafter(e.start_list[j], 0.0), std::nextafter(e.start_list[j], 2.0)})
-                    if (x >= 0.0 && x < 1.0) us.push_back(x);
-            for (double u : us) {
-                uint32_t got = 0;
-                for (uint32_t j = 0; j < e.n_list; ++j)
-                    if (e.start_list[j] > u) { got = cells[j]; break; }
-                if (got != linear_sample(e.cdf, u)) return fail(RL_E_STATE, "start list differs from categorical_sample");
-            }
-        }
-    } else if (!e.map.empty() && e.fixed_start != 0) {
-        // the built-in maps' kernels reset to the constant 0 (rl_device.h)
-        return fail(RL_E_STATE, "built-in FrozenLake map does not start at position 0");
-    }
-    return RL_OK;
-}
-
-// NeuralPolicy input features of every dense state (rl.h rl_input_adapter)
-int net_feature_table(const rl_env_config &c, const EnvHost &e, int input, std::vector<double> &feat, uint32_t &n_in) {
-    if (input == RL_INPUT_FL_OBS) {
-        if (e.map.empty()) return fail(RL_E_ARG, "the FrozenLakeObs adapter needs FrozenLake / FrozenLakeEdited");
-        n_in = 6;
-        feat.assign((size_t)e.S * 6, 0.0);
-        for (uint32_t s = 0; s < e.S; ++s) {
-            const int row = (int)s / e.ncol, col = (int)s % e.ncol;   // x = row, y = col (frozen_lake_edited.rs:146-147)
-            for (int a = 0; a < 4; ++a)
-                feat[s * 6 + a] = terrain_value(neighbour(e.map, e.nrow, e.ncol, row, col, a));
-            feat[s * 6 + 4] = (double)row;
-            feat[s * 6 + 5] = (double)col;
-        }
-        return RL_OK;
-    }
-    if (input != RL_INPUT_SCALAR) return fail(RL_E_ARG, "unknown input adapter");
-    if (c.kind == RL_ENV_FROZEN_LAKE_EDITED)
-        return fail(RL_E_ARG, "FrozenLakeEdited observations are FrozenLakeObs structs: use RL_INPUT_FL_OBS");
-    n_in = 1;
-    feat.assign(e.S, 0.0);
-    for (uint32_t s = 0; s < e.S; ++s) feat[s] = (double)rl_obs_to_reference(c.kind, s);   // obs as f64
-    return RL_OK;
-}
 // rand 0.8.5 UniformFloat::<f64>::new(low, high): scale decreased until
 // scale * max_rand + low < high
 double uniform_scale(double low, double high) {
@@ -446,18 +105,60 @@ int merge_headroom(uint64_t groups) {
     return h - 10 > 0 ? h - 10 : 0;
 }
 
+// A hipMalloc'd array its handle owns: freed with the handle, moved but never copied.
+// It converts to the raw pointer KParams / PopParams and the HIP calls take.
+struct HipFree { void operator()(void *p) const { (void)hipFree(p); } };
 template <class T>
-int dalloc(T **p, size_t n) {
-    *p = nullptr;
-    if (n == 0) return RL_OK;
-    HIPC(hipMalloc((void **)p, n * sizeof(T)));
-    return RL_OK;
-}
-template <class T>
-void dfree(T *&p) {
-    if (p) (void)hipFree((void *)p);
-    p = nullptr;
-}
+class DevBuf {
+    std::unique_ptr<T, HipFree> p_;
+    size_t n_ = 0;
+
+public:
+    // n elements (what it held is freed first); n == 0 leaves it null
+    int alloc(size_t n) {
+        reset();
+        if (n == 0) return RL_OK;
+        T *q = nullptr, **p = &q;
+        HIPC(hipMalloc((void **)p, n * sizeof(T)));
+        reset(q, n);
+        return RL_OK;
+    }
+    // its size() elements copied in from `src` (a failed copy: RL_E_HIP, `what`)
+    int fill(const T *src, const char *what) const {
+        const bool ok = !n_ || hipMemcpy(get(), src, n_ * sizeof(T), hipMemcpyHostToDevice) == hipSuccess;
+        return ok ? RL_OK : fail(RL_E_HIP, what);
+    }
+    // frees what it holds and takes over `p` (memory hipFree releases)
+    void reset(T *p = nullptr, size_t n = 0) { p_.reset(p); n_ = n; }
+    T *get() const { return p_.get(); }
+    size_t size() const { return n_; }
+    operator T *() const { return get(); }
+};
+static_assert(!std::is_copy_constructible<DevBuf<double>>::value, "a device array has one owner");
+
+// The env tables on the device: an EnvHost's `trans` and start cdf, uploaded once,
+// and the one place that writes the env fields of a KParams — for the handle that
+// owns the tables and for an Env view of it (rl_agent_env) alike.
+struct EnvTables {
+    DevBuf<uint32_t> trans;
+    DevBuf<double> cdf;
+    int alloc(const EnvHost &eh) {
+        if (int rc = trans.alloc(eh.trans.size())) return rc;
+        return cdf.alloc(eh.dev_cdf().size());
+    }
+    // made once the handle's other arrays are allocated (the order matters: profiles/host_refactor.md)
+    int upload(const EnvHost &eh) const {
+        if (int rc = trans.fill(eh.trans.data(), "table upload")) return rc;
+        return cdf.fill(eh.dev_cdf().data(), "table upload");
+    }
+    void params(const EnvHost &eh, KParams &p) const {
+        p.trans = trans; p.start_cdf = cdf; p.n_start = eh.dev_n_start();
+        p.fixed_start = eh.fixed_start;
+        p.slippery = eh.slippery;
+        p.max_steps = eh.max_steps; p.th1 = eh.th1; p.th2 = eh.th2; p.th3 = eh.th3;
+        p.trunc_reward = eh.trunc_reward;
+    }
+};
 
 }  // namespace
 
@@ -479,23 +180,22 @@ struct rl_comm {
     double *vals = nullptr;
     uint32_t n_vals = 0;
 };
-struct rl_env {
+struct __attribute__((visibility("hidden"))) rl_env {   // its destructor stays out of the exports
     rl_env_config cfg{};
     EnvHost eh;
     int device = 0;
     hipStream_t stream = nullptr;
     // an Env view of an agent's lanes (rl_agent_env): lane records, RNG streams and
-    // tables are the agent's, calls run on the agent's stream
+    // tables are the agent's (borrowed through `kp`), calls run on the agent's stream
     bool view = false;
     rl_agent *owner = nullptr;
     uint32_t L = 0;
-    uint4 *core = nullptr, *rng = nullptr;
-    uint32_t *trans = nullptr;
-    double *cdf = nullptr;
-    uint32_t *act_d = nullptr;
-    uint64_t *obs_d = nullptr;
-    double *rew_d = nullptr;
-    uint8_t *term_d = nullptr;
+    DevBuf<uint4> core, rng;
+    EnvTables tables;
+    DevBuf<uint32_t> act_d;
+    DevBuf<uint64_t> obs_d;
+    DevBuf<double> rew_d;
+    DevBuf<uint8_t> term_d;
     std::vector<uint8_t> ready;
     // a view's lanes moved under it (a train launch of its agent): ready is re-read
     // from the lane records (LF_READY) before the next call uses it
@@ -511,64 +211,66 @@ struct rl_agent {
     uint32_t S = 0, A = 0, P = 1, L = 0, G = 1, K = 1;
     bool priv = false;
     // lanes
-    uint4 *core = nullptr, *rng = nullptr, *aux = nullptr;
-    double *epi_reward = nullptr;
+    DevBuf<uint4> core, rng, aux;
+    DevBuf<double> epi_reward;
     // shared
-    int64_t *q_base = nullptr;   // fixed-point words or f64 bits (qrepr)
-    uint64_t *n_base = nullptr;
-    uint64_t *t_base = nullptr;
+    DevBuf<int64_t> q_base;   // fixed-point words or f64 bits (qrepr)
+    DevBuf<uint64_t> n_base;
+    DevBuf<uint64_t> t_base;
     // merge buffer [MAX words][SUM words] (merge_layout), own or the caller's:
     // delta_cap words at delta_max, delta = delta_max + the MAX words
-    int64_t *delta_own = nullptr, *delta_max = nullptr, *delta = nullptr, *delta_rep = nullptr;
+    DevBuf<int64_t> delta_own, delta_rep;
+    int64_t *delta_max = nullptr, *delta = nullptr;
     uint64_t delta_words = 0;    // replica stride: the dense SUM layout
     uint64_t delta_cap = 0;
     bool merge_groups_set = false;   // rl_agent_set_merge_groups / set_comm declared the total
     uint32_t n_rep = 1;
-    uint64_t *qslot = nullptr;   // f64 merge: every group's final Q [n_groups][psal]
+    DevBuf<uint64_t> qslot;   // f64 merge: every group's final Q [n_groups][psal]
     uint32_t n_groups = 0, psal = 0;
     uint64_t merge_groups = 0;   // learner groups over every rank
     int qrepr = RL_QREPR_FIXED40;
     int q_forced = 0;            // rl_agent_set_q_mode(RL_QMODE_F64)
     // private
-    double *q_priv = nullptr;
-    uint64_t *n_priv = nullptr;
-    uint64_t *t_priv = nullptr;
+    DevBuf<double> q_priv;
+    DevBuf<uint64_t> n_priv;
+    DevBuf<uint64_t> t_priv;
     // traces
-    double *trace = nullptr;
-    uint16_t *tlist = nullptr, *slot_of = nullptr;
-    uint32_t *tcnt = nullptr, *vbits = nullptr;
+    DevBuf<double> trace;
+    DevBuf<uint16_t> tlist, slot_of;
+    DevBuf<uint32_t> tcnt, vbits;
     size_t vbits_words = 0;
     int trace_layout = -1;   // layout_sparse_traces() of the kernel the trace sets were built for
     // Dyna model (private mode)
     uint32_t plan = 0;
-    uint32_t *mcnt = nullptr, *mslot = nullptr;
-    uint4 *mrec = nullptr;
+    DevBuf<uint32_t> mcnt, mslot;
+    DevBuf<uint4> mrec;
     // NeuralPolicy
     bool neural = false;
     uint32_t n_in = 0, n_params = 0, net_gen = 0xffffffffu;
-    double *net_w = nullptr, *feat = nullptr;
+    DevBuf<double> net_w, feat;
     // env tables
-    uint32_t *trans = nullptr;
-    double *cdf = nullptr;
+    EnvTables tables;
     // outputs
-    unsigned long long *stats_d = nullptr;
-    rl_step_record *rec_d = nullptr;
+    DevBuf<unsigned long long> stats_d;
+    DevBuf<rl_step_record> rec_d;
     bool recording = false;
     std::vector<rl_step_record> rec_h;
-    rl_episode_record *elog_d = nullptr;   // episode log ring [cap][L]
-    uint32_t *elog_cnt_d = nullptr;
+    DevBuf<rl_episode_record> elog_d;   // episode log ring [cap][L]
+    DevBuf<uint32_t> elog_cnt_d;
     uint32_t elog_cap = 0;
     uint64_t launches = 0;
     bool timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
     // train()/evaluate() loop control (k_ctl_word): device {done, lanes, status},
     // two pinned host slots and their events (read one launch behind)
-    int64_t *ctl_d = nullptr, *ctl_h = nullptr;
+    DevBuf<int64_t> ctl_d;
+    int64_t *ctl_h = nullptr;
     hipEvent_t ctl_ev[2] = {nullptr, nullptr};
     KParams kp{};
     // per-call Agent surface (rl_agent_get_action / rl_agent_update): device
     // arrays of L entries and their pinned host staging
-    unsigned char *call_d = nullptr, *call_h = nullptr;
+    DevBuf<unsigned char> call_d;
+    unsigned char *call_h = nullptr;
     rl_env *env_view = nullptr;
     train_launch_fn fn = nullptr;
     dim3 grid, block;
@@ -585,12 +287,12 @@ struct rl_agent {
     // the one-shot peer-read merge (rl.h ABI 7, rl_misc.hip k_peer_reduce): this
     // rank's IPC-exported exchange region and every rank's mapping of it
     struct PeerMerge {
-        int64_t *region = nullptr;           // [2 slots][cap] words, then the epoch flag
+        DevBuf<int64_t> region;              // [2 slots][cap] words, then the epoch flag
         uint64_t cap = 0;                    // words per slot
         int32_t rank = 0, world = 1;
         std::vector<int64_t *> bases;        // rank order; the peers' are IPC mappings
-        int64_t **bases_d = nullptr;
-        uint32_t *err_d = nullptr;           // a wait that timed out
+        DevBuf<int64_t *> bases_d;
+        DevBuf<uint32_t> err_d;              // a wait that timed out
         int64_t epoch = 0;                   // merges made (every rank makes the same)
         int64_t timeout_ticks = 0;           // wall-clock ticks a rank waits for a peer
         bool on = false;
@@ -602,8 +304,8 @@ struct rl_agent {
     bool pop = false;
     uint32_t M = 0;
     std::vector<rl_member_config> members;
-    MemberParams *members_d = nullptr;
-    unsigned long long *pop_stats_d = nullptr;   // [M][STATS_W]
+    DevBuf<MemberParams> members_d;
+    DevBuf<unsigned long long> pop_stats_d;   // [M][STATS_W]
     pop_launch_fn pop_fn = nullptr;
     PopParams pp{};
 };
@@ -624,7 +326,6 @@ void agent_sync_params(rl_agent *a);
 // the peer-read merge's region handling (defined with the ABI 7 calls below)
 int peer_alloc(rl_agent *a);
 void peer_detach(rl_agent *a);
-void peer_free(rl_agent *a);
 int peer_check(rl_agent *a);
 int peer_selftest(rl_agent *a, bool *ok);
 
@@ -636,6 +337,24 @@ int lds_guard_fail(size_t need) {
 
 // tables held by the handle: a population keeps one per member
 size_t table_count(const rl_agent *a) { return a->pop ? a->M : 1; }
+
+// The shared-mode LDS carve of the handle's kernel (block of `nthr` threads, `trc_kb` KiB of pair-trace
+// slots) as shared_smem_bytes or shared_pair_cap reports it: the one place that spells their argument list
+template <class Of>
+auto shared_carve(const rl_agent *a, Of of, uint32_t nthr, uint32_t trc_kb) {
+    return of(a->eh.kenv, a->cfg.agent, a->cfg.policy, a->cfg.selector, a->cfg.algo, a->S, a->A, a->eh.dev_n_start(),
+              nthr, trc_kb, a->qrepr == RL_QREPR_F64, a->kp.ucb_pack);
+}
+
+// An experiment override: the integer in the variable `name` where `allowed` takes
+// it, else `dflt` (unset, or a value outside the set: ignored).  Read at every call.
+template <class Allowed>
+int env_override(const char *name, int dflt, Allowed allowed) {
+    const char *e = getenv(name);
+    if (!e) return dflt;
+    const int v = atoi(e);
+    return allowed(v) ? v : dflt;
+}
 
 // A population's launch shape: grid = members, block and LDS carve as a lone learner
 // group of G lanes gets them (64 lanes per wave, the `lpw` rule's doubling never
@@ -649,8 +368,7 @@ int population_select_kernel(rl_agent *a) {
     a->kp.trc_kb = 0;
     a->block = dim3(((a->G + 63) / 64) * 64);
     a->grid = dim3(a->M);
-    a->smem = shared_smem_bytes(a->eh.kenv, a->cfg.agent, a->cfg.policy, a->cfg.selector, a->cfg.algo, a->S, a->A,
-                                a->eh.dev_n_start(), a->block.x, 0, a->qrepr == RL_QREPR_F64, 0);
+    a->smem = shared_carve(a, shared_smem_bytes, a->block.x, 0);
     if (a->smem > 160 * 1024) return lds_guard_fail(a->smem);
     a->smem_v[0] = a->smem_v[1] = a->smem;
     a->trc_kb_v[0] = a->trc_kb_v[1] = 0;
@@ -683,25 +401,21 @@ int agent_select_kernel(rl_agent *a) {
         uint32_t lpw = (!a->neural && psa * 8 <= 4096 &&
                         (ek == RL_ENV_FROZEN_LAKE || ek == RL_ENV_CLIFF_WALKING || ek == RL_ENV_FROZEN_LAKE_EDITED))
                            ? 8u : 0u;
-        if (const char *e = getenv("RLAMD_PRIV_LPW")) {
-            const uint32_t v = (uint32_t)atoi(e);
-            if (v == 0 || v == 2 || v == 4 || v == 8 || v == 16 || v == 32 || v == 64) lpw = lpw ? v : 0u;
-        }
+        if (lpw)
+            lpw = (uint32_t)env_override("RLAMD_PRIV_LPW", (int)lpw, [](int v) {
+                return v == 0 || v == 2 || v == 4 || v == 8 || v == 16 || v == 32 || v == 64;
+            });
         // the bin's network (frozen_lake_neural.rs:130-134) on one-step agents: the
         // lane's parameters in registers for the launch (k_train_private_net);
         // RLAMD_NET_REGS=0 keeps them in HBM (experiments)
         a->kp.net_regs = 0;
         if (a->neural && a->cfg.agent == RL_AGENT_ONE_STEP && a->A == 4 && a->n_in == 1 &&
             a->cfg.net.hidden == 32 && a->cfg.net.act_hidden == RL_ACT_LEAKY_RELU6 &&
-            a->cfg.net.act_out == RL_ACT_LINEAR && ek == RL_ENV_FROZEN_LAKE) {
-            const char *e = getenv("RLAMD_NET_REGS");
-            a->kp.net_regs = (e && atoi(e) == 0) ? 0u : 1u;
-        }
-        uint32_t pwv = 4;   // waves per block (RLAMD_PRIV_WAVES = 1 / 2 / 4: experiments)
-        if (const char *e = getenv("RLAMD_PRIV_WAVES")) {
-            const uint32_t v = (uint32_t)atoi(e);
-            if (v == 1 || v == 2 || v == 4) pwv = v;
-        }
+            a->cfg.net.act_out == RL_ACT_LINEAR && ek == RL_ENV_FROZEN_LAKE)
+            a->kp.net_regs = (uint32_t)env_override("RLAMD_NET_REGS", 1, [](int v) { return v == 0; });
+        // waves per block (RLAMD_PRIV_WAVES = 1 / 2 / 4: experiments)
+        const uint32_t pwv =
+            (uint32_t)env_override("RLAMD_PRIV_WAVES", 4, [](int v) { return v == 1 || v == 2 || v == 4; });
         if (lpw) {
             const uint32_t nl = pwv * lpw;
             const size_t smem = ((a->smem + 15) & ~(size_t)15) + (size_t)nl * (psa + 2) * 8;
@@ -715,6 +429,8 @@ int agent_select_kernel(rl_agent *a) {
     } else {
         a->kp.ucb_pack = (uint64_t)a->G * a->K < 65536ull ? 1 : 0;   // UCB + expected SARSA counters (KParams)
         const uint32_t g = std::min(a->G, a->L);
+        int ncu = 256;   // the device's CUs: the lanes-per-wave rule and the groups per CU below
+        (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, a->device);
         // lanes per wave (rl_kparams.h KParams::lpw): 64, or 32 for the pair-pool
         // traces kernel (small tables) when the lanes give fewer than 4 waves per
         // SIMD at 64: the pool sweep is latency-bound and a wave sweeps its lanes'
@@ -731,14 +447,9 @@ int agent_select_kernel(rl_agent *a) {
                               (ek == RL_ENV_CLIFF_WALKING || ek == RL_ENV_FROZEN_LAKE ||
                                ek == RL_ENV_FROZEN_LAKE_EDITED) &&
                               !env_wide(a->eh.kenv);   // wide maps run the pair lists, not the pool
-            int ncu = 256;
-            (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, a->device);
             if (pool && ((uint64_t)a->L + 63u) / 64u < 16ull * (uint64_t)ncu) lpw = 32;
         }
-        if (const char *e = getenv("RLAMD_LPW")) {
-            const uint32_t v = (uint32_t)atoi(e);
-            if (v == 16 || v == 32 || v == 64) lpw = v;
-        }
+        lpw = (uint32_t)env_override("RLAMD_LPW", (int)lpw, [](int v) { return v == 16 || v == 32 || v == 64; });
         while ((g + lpw - 1) / lpw > 16) lpw *= 2;   // <= 1024 threads per block
         a->kp.lpw = lpw;
         a->block = dim3(((g + lpw - 1) / lpw) * 64);
@@ -751,12 +462,8 @@ int agent_select_kernel(rl_agent *a) {
         // 16 slots 6.6e9, 25 slots 7.0e9 env-steps/s; 1 group per CU 3.9e9.
         // RLAMD_TRC_KB overrides (experiments)
         {
-            int ncu = 256;
-            (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, a->device);
             const uint64_t groups = a->grid.x, per_cu = (groups + (uint64_t)ncu - 1) / (uint64_t)ncu;
-            const size_t base = shared_smem_bytes(a->eh.kenv, a->cfg.agent, a->cfg.policy, a->cfg.selector,
-                                                  a->cfg.algo, a->S, a->A, a->eh.dev_n_start(), a->block.x, 0,
-                                                  a->qrepr == RL_QREPR_F64, a->kp.ucb_pack);
+            const size_t base = shared_carve(a, shared_smem_bytes, a->block.x, 0);
             // tables that cannot fit are rejected here, before the occupancy query below
             // would ask the runtime for an impossible carve (and leave its error behind)
             if (base > 160 * 1024) return lds_guard_fail(base);
@@ -785,13 +492,9 @@ int agent_select_kernel(rl_agent *a) {
             a->kp.episodic = epi_saved;
         }
         for (int epi = 0; epi < 2; ++epi) {
-            if (const char *e = getenv("RLAMD_TRC_KB")) {
-                const int v = atoi(e);
-                if (v >= 0 && v <= 150) a->trc_kb_v[epi] = (uint32_t)v;
-            }
-            a->smem_v[epi] = shared_smem_bytes(a->eh.kenv, a->cfg.agent, a->cfg.policy, a->cfg.selector,
-                                               a->cfg.algo, a->S, a->A, a->eh.dev_n_start(), a->block.x,
-                                               a->trc_kb_v[epi], a->qrepr == RL_QREPR_F64, a->kp.ucb_pack);
+            a->trc_kb_v[epi] = (uint32_t)env_override("RLAMD_TRC_KB", (int)a->trc_kb_v[epi],
+                                                      [](int v) { return v >= 0 && v <= 150; });
+            a->smem_v[epi] = shared_carve(a, shared_smem_bytes, a->block.x, a->trc_kb_v[epi]);
             if (a->smem_v[epi] > 160 * 1024) return lds_guard_fail(a->smem_v[epi]);
         }
         const int ep = a->kp.episodic ? 1 : 0;
@@ -1136,9 +839,7 @@ int launch_train_kernel(rl_agent *a, bool *merge = nullptr) {
     // cap, so a launch with another cap rebuilds them for its own first
     if (!a->priv && a->vbits && a->tcnt && pair_slot_index_env(a->eh.kenv) &&
         layout_sparse_traces(a->cfg.agent, a->cfg.selector, a->cfg.algo, 0)) {
-        const uint32_t cap = shared_pair_cap(a->eh.kenv, a->cfg.agent, a->cfg.policy, a->cfg.selector,
-                                             a->cfg.algo, a->S, a->A, a->eh.dev_n_start(), a->block.x,
-                                             a->kp.trc_kb, a->qrepr == RL_QREPR_F64, a->kp.ucb_pack);
+        const uint32_t cap = shared_carve(a, shared_pair_cap, a->block.x, a->kp.trc_kb);
         if (a->pair_cap_last != UINT32_MAX && cap != a->pair_cap_last) {
             launch_pair_reindex(a->kp, cap, a->stream);
             HIPC(hipGetLastError());
@@ -1399,180 +1100,6 @@ int rl_device_count(int *count) {
     return RL_OK;
 }
 
-uint64_t rl_blackjack_obs_id(uint32_t p, uint32_t d, uint32_t ace) {
-    // fxhash 0.2.1: FxHasher64::write_u8 per field of #[derive(Hash)]
-    const uint64_t K = 0x517cc1b727220a95ull;
-    uint64_t h = 0;
-    const uint64_t w[3] = {p & 0xffu, d & 0xffu, ace ? 1u : 0u};
-    for (uint64_t x : w) h = (((h << 5) | (h >> 59)) ^ x) * K;
-    return h;
-}
-uint64_t rl_obs_to_reference(int32_t env_kind, uint32_t s) {
-    if (env_kind == RL_ENV_BLACKJACK) return rl_blackjack_obs_id(s >> 6, (s >> 1) & 31u, s & 1u);
-    return s;
-}
-int rl_obs_from_reference(int32_t env_kind, uint64_t obs, uint32_t *dense_state) {
-    if (!dense_state) return fail(RL_E_ARG, "null argument");
-    if (env_kind != RL_ENV_BLACKJACK) {
-        if (obs > 0xffffffffull) return fail(RL_E_ARG, "observation out of range");
-        *dense_state = (uint32_t)obs;
-        return RL_OK;
-    }
-    // the 2048 dense Blackjack observations by their fxhash ids (distinct: checked once)
-    static const std::vector<std::pair<uint64_t, uint32_t>> ids = [] {
-        std::vector<std::pair<uint64_t, uint32_t>> v(2048);
-        for (uint32_t s = 0; s < 2048; ++s) v[s] = {rl_obs_to_reference(RL_ENV_BLACKJACK, s), s};
-        std::sort(v.begin(), v.end());
-        return v;
-    }();
-    const auto it = std::lower_bound(ids.begin(), ids.end(), std::make_pair(obs, 0u));
-    if (it == ids.end() || it->first != obs) return fail(RL_E_ARG, "not a Blackjack observation id");
-    *dense_state = it->second;
-    return RL_OK;
-}
-
-// rl_map_register / rl_map_register_wide: one validation and one registry; `cap` is
-// the format's cell limit and `cap_name` its name in the messages
-static int map_register(const char *const *rows, uint32_t n_rows, int32_t *map_id, size_t cap, const char *cap_name,
-                        bool wide) {
-    if (!rows || !map_id) return fail(RL_E_ARG, "null argument");
-    if (n_rows == 0) return fail(RL_E_ARG, "a map needs at least one row");
-    Grid g;
-    for (uint32_t r = 0; r < n_rows; ++r) {
-        if (!rows[r]) return fail(RL_E_ARG, "null map row " + std::to_string(r));
-        // the length is bounded while it is measured: a row is never read past the cell limit
-        const size_t len = strnlen(rows[r], cap + 1);
-        if (len == 0) return fail(RL_E_ARG, "map row " + std::to_string(r) + " has zero columns");
-        if (r > 0 && len != g[0].size())
-            return fail(RL_E_ARG, "ragged map: row " + std::to_string(r) + " has " +
-                                      (len > cap ? "more than " + std::to_string(cap) : std::to_string(len)) +
-                                      " columns, row 0 has " + std::to_string(g[0].size()));
-        if ((size_t)n_rows * len > cap)
-            return fail(RL_E_ARG, std::string("map has more than ") + cap_name + " (" + std::to_string(cap) + ") cells");
-        for (size_t i = 0; i < len; ++i) {
-            const char ch = rows[r][i];
-            if (ch != 'S' && ch != 'F' && ch != 'H' && ch != 'G')
-                return fail(RL_E_ARG, std::string("map letter outside SFHG at row ") + std::to_string(r) + ", column " +
-                                          std::to_string(i));
-        }
-        g.emplace_back(rows[r], len);
-    }
-    std::lock_guard<std::mutex> lock(g_map_mu);
-    std::vector<Grid> &maps = map_registry();
-    std::vector<uint8_t> &flags = map_wide_flags();
-    for (size_t i = 2; i < maps.size(); ++i)
-        if (maps[i] == g && (flags[i] != 0) == wide) { *map_id = (int32_t)i; return RL_OK; }
-    if (maps.size() >= (size_t)INT32_MAX) return fail(RL_E_ARG, "map registry full");
-    maps.push_back(std::move(g));
-    flags.push_back(wide ? 1 : 0);
-    *map_id = (int32_t)(maps.size() - 1);
-    return RL_OK;
-}
-
-int rl_map_register(const char *const *rows, uint32_t n_rows, int32_t *map_id) {
-    return map_register(rows, n_rows, map_id, RL_MAP_MAX_CELLS, "RL_MAP_MAX_CELLS", false);
-}
-
-int rl_map_register_wide(const char *const *rows, uint32_t n_rows, int32_t *map_id) {
-    return map_register(rows, n_rows, map_id, RL_MAP_WIDE_MAX_CELLS, "RL_MAP_WIDE_MAX_CELLS", true);
-}
-
-int rl_map_is_wide(int32_t map_id, int32_t *wide) {
-    if (!wide) return fail(RL_E_ARG, "null argument");
-    Grid g;
-    bool w = false;
-    if (!map_lookup(map_id, g, &w))
-        return fail(RL_E_ARG, "unknown FrozenLake map id " + std::to_string(map_id));
-    *wide = w ? 1 : 0;
-    return RL_OK;
-}
-
-int rl_map_info(int32_t map_id, uint32_t *n_rows, uint32_t *n_cols, char *cells, size_t n) {
-    Grid g;
-    if (!map_lookup(map_id, g))
-        return fail(RL_E_ARG, "unknown FrozenLake map id " + std::to_string(map_id));
-    const size_t nr = g.size(), nc = g[0].size();
-    if (n_rows) *n_rows = (uint32_t)nr;
-    if (n_cols) *n_cols = (uint32_t)nc;
-    if (cells) {
-        if (n != nr * nc) return fail(RL_E_ARG, "cells must hold rows * cols = " + std::to_string(nr * nc) + " chars");
-        for (size_t r = 0; r < nr; ++r) std::memcpy(cells + r * nc, g[r].data(), nc);
-    }
-    return RL_OK;
-}
-
-int rl_env_dims(const rl_env_config *cfg, uint32_t *S, uint32_t *A) {
-    if (!cfg || !S || !A) return fail(RL_E_ARG, "null argument");
-    EnvHost e;
-    int rc = build_env(*cfg, e);
-    if (rc) return rc;
-    *S = e.S;
-    *A = e.A;
-    return RL_OK;
-}
-
-int rl_env_table(const rl_env_config *cfg, double *prob, uint32_t *next, double *reward, uint8_t *term,
-                 double *start) {
-    if (!cfg) return fail(RL_E_ARG, "null config");
-    EnvHost e;
-    int rc = build_env(*cfg, e);
-    if (rc) return rc;
-    if (e.kind == RL_ENV_BLACKJACK) return fail(RL_E_ARG, "Blackjack has no transition table");
-    for (uint32_t s = 0; s < e.S; ++s)
-        for (uint32_t a = 0; a < e.A; ++a) {
-            const uint32_t w = env_wide(e.kenv) ? 0u : e.trans[s * e.A + a];
-            const size_t k = ((size_t)s * e.A + a) * 3;
-            double pr[3] = {1.0, 0.0, 0.0};
-            uint32_t nx[3] = {0, 0, 0};
-            double rw[3] = {0.0, 0.0, 0.0};
-            uint8_t tm[3] = {0, 0, 0};
-            if (e.kind == RL_ENV_FROZEN_LAKE || e.kind == RL_ENV_FROZEN_LAKE_EDITED) {
-                const bool edited = e.kind == RL_ENV_FROZEN_LAKE_EDITED;
-                const char cell = e.map[s / e.ncol][s % e.ncol];
-                if (env_wide(e.kenv)) {
-                    // the wide words as the device steps them: direction (a + 3 + i) & 3 on
-                    // a slippery map, a on a deterministic one; one outcome on 'G' / 'H'
-                    const uint16_t *t16 = (const uint16_t *)e.trans.data();
-                    const int n = (e.slippery && cell != 'G' && cell != 'H') ? 3 : 1;
-                    for (int i = 0; i < n; ++i) {
-                        const uint32_t o = t16[(size_t)s * 4 + (n == 3 ? ((a + 3u + (uint32_t)i) & 3u) : a)];
-                        pr[i] = n == 3 ? 1.0 / 3.0 : 1.0;
-                        nx[i] = o & WIDE_NEXT_MASK;
-                        rw[i] = edited ? ((o & WIDE_REWARD) ? 10.0 : -1.0) : ((o & WIDE_REWARD) ? 1.0 : 0.0);
-                        tm[i] = (o & WIDE_TERM) ? 1 : 0;
-                    }
-                } else {
-                    const int n = (w >> 24) & 1 ? 3 : 1;
-                    for (int i = 0; i < n; ++i) {
-                        const uint32_t o = (w >> (8 * i)) & 0xffu;
-                        pr[i] = n == 3 ? 1.0 / 3.0 : 1.0;
-                        nx[i] = o & 63u;
-                        rw[i] = edited ? ((o & 64u) ? 10.0 : -1.0) : ((o & 64u) ? 1.0 : 0.0);
-                        tm[i] = (o & 128u) ? 1 : 0;
-                    }
-                }
-                if (cell == 'G' || cell == 'H') rw[0] = 0.0;   // (1.0, s, 0.0, true) rows: never stepped from
-            } else if (e.kind == RL_ENV_CLIFF_WALKING) {
-                nx[0] = w & 63u;
-                rw[0] = (w & 64u) ? -100.0 : -1.0;
-                tm[0] = (w & 128u) ? 1 : 0;
-            } else {
-                nx[0] = w & 511u;
-                const uint32_t rc2 = (w >> 9) & 3u;
-                rw[0] = rc2 == 0 ? -1.0 : (rc2 == 1 ? -10.0 : 20.0);
-                tm[0] = (w >> 11) & 1u;
-            }
-            for (int i = 0; i < 3; ++i) {
-                if (prob) prob[k + i] = pr[i];
-                if (next) next[k + i] = nx[i];
-                if (reward) reward[k + i] = rw[i];
-                if (term) term[k + i] = tm[i];
-            }
-        }
-    if (start) std::memcpy(start, e.start.data(), e.S * sizeof(double));
-    return RL_OK;
-}
-
 // ---------------------------------------------------------------- Env
 int rl_env_create(const rl_env_config *cfg, uint32_t n, uint64_t seed, uint64_t lane_offset, int32_t device,
                   rl_env **out) {
@@ -1584,58 +1111,42 @@ int rl_env_create(const rl_env_config *cfg, uint32_t n, uint64_t seed, uint64_t 
     if (rc) { delete e; return rc; }
     e->device = device;
     e->L = n;
-    auto bad = [&](int code) { rl_env_destroy(e); return code; };
-    if (hipSetDevice(device) != hipSuccess) return bad(fail(RL_E_HIP, "hipSetDevice failed (no GPU?)"));
+    std::unique_ptr<rl_env, decltype(&rl_env_destroy)> h(e, rl_env_destroy);   // a later failure destroys it
+    if (hipSetDevice(device) != hipSuccess) return fail(RL_E_HIP, "hipSetDevice failed (no GPU?)");
     if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess)
-        return bad(fail(RL_E_HIP, "hipStreamCreate failed"));
-    if ((rc = dalloc(&e->core, n)) || (rc = dalloc(&e->rng, n)) || (rc = dalloc(&e->act_d, n)) ||
-        (rc = dalloc(&e->obs_d, n)) || (rc = dalloc(&e->rew_d, n)) || (rc = dalloc(&e->term_d, n)) ||
-        (rc = dalloc(&e->trans, e->eh.trans.size())) || (rc = dalloc(&e->cdf, e->eh.dev_cdf().size())))
-        return bad(rc);
-    if (!e->eh.trans.empty() &&
-        hipMemcpy(e->trans, e->eh.trans.data(), e->eh.trans.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-        return bad(fail(RL_E_HIP, "table upload"));
-    if (!e->eh.dev_cdf().empty() &&
-        hipMemcpy(e->cdf, e->eh.dev_cdf().data(), e->eh.dev_cdf().size() * 8, hipMemcpyHostToDevice) != hipSuccess)
-        return bad(fail(RL_E_HIP, "table upload"));
+        return fail(RL_E_HIP, "hipStreamCreate failed");
+    if ((rc = e->core.alloc(n)) || (rc = e->rng.alloc(n)) || (rc = e->act_d.alloc(n)) || (rc = e->obs_d.alloc(n)) ||
+        (rc = e->rew_d.alloc(n)) || (rc = e->term_d.alloc(n)) || (rc = e->tables.alloc(e->eh)) ||
+        (rc = e->tables.upload(e->eh)))
+        return rc;
     KParams &p = e->kp;
     p.L = n; p.S = e->eh.S; p.A = e->eh.A; p.P = 1;
     p.core = e->core; p.rng = e->rng;
-    p.trans = e->trans; p.start_cdf = e->cdf; p.n_start = e->eh.dev_n_start();
-    p.fixed_start = e->eh.fixed_start;
-    p.slippery = e->eh.slippery;
-    p.max_steps = e->eh.max_steps; p.th1 = e->eh.th1; p.th2 = e->eh.th2; p.th3 = e->eh.th3;
-    p.trunc_reward = e->eh.trunc_reward;
+    e->tables.params(e->eh, p);
     // lane init needs aux/epi_reward: use scratch
-    uint4 *aux = nullptr;
-    double *er = nullptr;
-    if ((rc = dalloc(&aux, n)) || (rc = dalloc(&er, n))) return bad(rc);
+    DevBuf<uint4> aux;
+    DevBuf<double> er;
+    if ((rc = aux.alloc(n)) || (rc = er.alloc(n))) return rc;
     p.aux = aux; p.epi_reward = er;
     launch_lane_init(cfg->kind, p, seed, lane_offset, 0.0, e->stream);
     hipError_t he = hipStreamSynchronize(e->stream);
-    dfree(aux);
-    dfree(er);
     p.aux = nullptr; p.epi_reward = nullptr;
-    if (he != hipSuccess) return bad(fail(RL_E_HIP, hipGetErrorString(he)));
+    if (he != hipSuccess) return fail(RL_E_HIP, hipGetErrorString(he));
     e->ready.assign(n, 0);
-    *out = e;
+    *out = h.release();
     return RL_OK;
 }
 
 void rl_env_destroy(rl_env *e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
-    if (e->view) {   // the agent owns the lanes and tables
-        if (e->owner) {
-            (void)hipStreamSynchronize(e->owner->stream);
-            e->owner->env_view = nullptr;
-        }
-    } else {
-        dfree(e->core); dfree(e->rng); dfree(e->trans); dfree(e->cdf);
+    if (e->view && e->owner) {   // the agent owns the lanes and tables
+        (void)hipStreamSynchronize(e->owner->stream);
+        e->owner->env_view = nullptr;
     }
-    dfree(e->act_d); dfree(e->obs_d); dfree(e->rew_d); dfree(e->term_d);
-    if (e->stream) (void)hipStreamDestroy(e->stream);
-    delete e;
+    const hipStream_t stream = e->stream;
+    delete e;   // frees its device arrays
+    if (stream) (void)hipStreamDestroy(stream);
 }
 
 namespace {
@@ -1737,6 +1248,50 @@ int rl_env_step_lane(rl_env *e, uint32_t lane, uint32_t action, uint64_t *obs, d
     return RL_OK;
 }
 
+// The creators' host part (no HIP call): the env tables and the handle's dimensions
+static int agent_host_init(rl_agent *a, const rl_agent_config &c) {
+    a->cfg = c;
+    if (int rc = build_env(c.env, a->eh)) return rc;
+    a->device = c.device;
+    a->S = a->eh.S; a->A = a->eh.A; a->P = c.policy == RL_POLICY_DOUBLE ? 2 : 1;
+    a->L = c.n_lanes; a->G = c.group_size; a->K = c.sync_every;
+    return RL_OK;
+}
+// The creators' device part, from the first HIP call on: the stream, the lane arrays,
+// the stats replicas, the env tables, the caller's T shared-mode tables, and the KParams
+// fields that name them; the rest differs between the two
+static int agent_device_setup(rl_agent *a, size_t T) {
+    if (hipSetDevice(a->device) != hipSuccess) return fail(RL_E_HIP, "hipSetDevice failed (no GPU?)");
+    if (hipStreamCreateWithFlags(&a->own_stream, hipStreamNonBlocking) != hipSuccess)
+        return fail(RL_E_HIP, "hipStreamCreate failed");
+    a->stream = a->own_stream;
+    const size_t L = a->L, SA = (size_t)a->S * a->A;
+    int rc;
+    if ((rc = a->core.alloc(L)) || (rc = a->rng.alloc(L)) || (rc = a->aux.alloc(L)) || (rc = a->epi_reward.alloc(L)) ||
+        (rc = a->stats_d.alloc(STATS_W * STATS_REP)) || (rc = a->tables.alloc(a->eh)) ||
+        (rc = a->q_base.alloc(T * a->P * SA)) || (rc = a->n_base.alloc(T * SA)) || (rc = a->t_base.alloc(T)))
+        return rc;
+    KParams &p = a->kp;
+    p.L = a->L; p.G = a->G; p.K = a->K; p.S = a->S; p.A = a->A; p.P = a->P;
+    p.core = a->core; p.rng = a->rng; p.aux = a->aux; p.epi_reward = a->epi_reward;
+    p.q_base = a->q_base; p.n_base = a->n_base; p.t_base = a->t_base;   // (population) member 0's; each block takes its own
+    a->tables.params(a->eh, p);
+    p.target_episodes = 0; p.eval_at = 0; p.eval_div = 0; p.eval_episodes = a->cfg.eval_episodes; p.eval_only = 0;
+    p.stats = a->stats_d;
+    p.rec = nullptr;
+    return RL_OK;
+}
+// ... and, once the creator's own arrays are allocated, the env tables' upload and the loop-control word, slots, events
+static int agent_ctl_setup(rl_agent *a) {
+    int rc;
+    if ((rc = a->tables.upload(a->eh)) || (rc = a->ctl_d.alloc(3))) return rc;
+    if (hipHostMalloc((void **)&a->ctl_h, 6 * 8, hipHostMallocDefault) != hipSuccess ||
+        hipEventCreateWithFlags(&a->ctl_ev[0], hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&a->ctl_ev[1], hipEventDisableTiming) != hipSuccess)
+        return fail(RL_E_HIP, "loop control buffers");
+    return RL_OK;
+}
+
 // ---------------------------------------------------------------- Agent
 int rl_agent_create(const rl_agent_config *cfg, rl_agent **out) {
     if (!cfg || !out) return fail(RL_E_ARG, "null argument");
@@ -1755,90 +1310,63 @@ int rl_agent_create(const rl_agent_config *cfg, rl_agent **out) {
             return fail(RL_E_ARG, "activation out of range (softmax: output layer only)");
     }
     rl_agent *a = new rl_agent();
-    a->cfg = c;
-    int rc = build_env(c.env, a->eh);
+    int rc = agent_host_init(a, c);
     if (rc) { delete a; return rc; }
-    auto bad = [&](int code) { rl_agent_destroy(a); return code; };
-    a->device = c.device;
-    a->S = a->eh.S; a->A = a->eh.A; a->P = c.policy == RL_POLICY_DOUBLE ? 2 : 1;
-    a->L = c.n_lanes; a->G = c.group_size; a->K = c.sync_every;
     a->priv = a->G == 1;
-    if (hipSetDevice(c.device) != hipSuccess) return bad(fail(RL_E_HIP, "hipSetDevice failed (no GPU?)"));
-    if (hipStreamCreateWithFlags(&a->own_stream, hipStreamNonBlocking) != hipSuccess)
-        return bad(fail(RL_E_HIP, "hipStreamCreate failed"));
-    a->stream = a->own_stream;
+    std::unique_ptr<rl_agent, decltype(&rl_agent_destroy)> h(a, rl_agent_destroy);   // a later failure destroys it
+    if ((rc = agent_device_setup(a, a->priv ? 0 : 1))) return rc;   // shared mode: one table
     const size_t L = a->L, SA = (size_t)a->S * a->A, PSA = a->P * SA;
-    if ((rc = dalloc(&a->core, L)) || (rc = dalloc(&a->rng, L)) || (rc = dalloc(&a->aux, L)) ||
-        (rc = dalloc(&a->epi_reward, L)) || (rc = dalloc(&a->stats_d, STATS_W * STATS_REP)) ||
-        (rc = dalloc(&a->trans, a->eh.trans.size())) || (rc = dalloc(&a->cdf, a->eh.dev_cdf().size())))
-        return bad(rc);
     a->neural = c.policy == RL_POLICY_NEURAL;
     if (a->neural) {
         std::vector<double> feat;
-        if ((rc = net_feature_table(c.env, a->eh, c.net.input, feat, a->n_in))) return bad(rc);
+        if ((rc = net_feature_table(c.env, a->eh, c.net.input, feat, a->n_in))) return rc;
         a->n_params = a->n_in * c.net.hidden + c.net.hidden + c.net.hidden * a->A + a->A;
-        if ((rc = dalloc(&a->net_w, (size_t)a->n_params * L)) || (rc = dalloc(&a->feat, feat.size()))) return bad(rc);
-        if (hipMemcpy(a->feat, feat.data(), feat.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
-            return bad(fail(RL_E_HIP, "feature upload"));
+        if ((rc = a->net_w.alloc((size_t)a->n_params * L)) || (rc = a->feat.alloc(feat.size())) ||
+            (rc = a->feat.fill(feat.data(), "feature upload")))
+            return rc;
     }
     if (a->priv) {
-        if (!a->neural && (rc = dalloc(&a->q_priv, PSA * L))) return bad(rc);
+        if (!a->neural && (rc = a->q_priv.alloc(PSA * L))) return rc;
         // UCB counters are allocated even for eps-greedy: set_action_selector may switch
-        if ((rc = dalloc(&a->n_priv, SA * L)) || (rc = dalloc(&a->t_priv, L))) return bad(rc);
+        if ((rc = a->n_priv.alloc(SA * L)) || (rc = a->t_priv.alloc(L))) return rc;
     } else {
         a->delta_words = 2 * PSA + SA + 1 + 3 * PSA;
         const uint32_t n_groups = (a->L + a->G - 1) / a->G;
         a->n_groups = n_groups;
         a->merge_groups = n_groups;
         // merge buffer [PSA MAX words][delta_words SUM words]; f64 slots for every group
-        if ((rc = dalloc(&a->q_base, PSA)) || (rc = dalloc(&a->n_base, SA)) || (rc = dalloc(&a->t_base, 1)) ||
-            (rc = dalloc(&a->delta_own, PSA + a->delta_words)) || (rc = dalloc(&a->qslot, (size_t)n_groups * PSA)))
-            return bad(rc);
+        if ((rc = a->delta_own.alloc(PSA + a->delta_words)) || (rc = a->qslot.alloc((size_t)n_groups * PSA))) return rc;
         a->delta_max = a->delta_own;
         a->delta = a->delta_own + PSA;
         a->delta_cap = PSA + a->delta_words;   // the largest layout: f64 over dense rows
-        if (hipMemset(a->delta_own, 0, (PSA + a->delta_words) * 8) != hipSuccess) return bad(fail(RL_E_HIP, "memset"));
+        if (hipMemset(a->delta_own, 0, (PSA + a->delta_words) * 8) != hipSuccess) return fail(RL_E_HIP, "memset");
         a->n_rep = std::min<uint32_t>(64u, n_groups);
-        if ((rc = dalloc(&a->delta_rep, a->delta_words * a->n_rep))) return bad(rc);
-        if (hipMemset(a->delta_rep, 0, a->delta_words * a->n_rep * 8) != hipSuccess)
-            return bad(fail(RL_E_HIP, "memset"));
+        if ((rc = a->delta_rep.alloc(a->delta_words * a->n_rep))) return rc;
+        if (hipMemset(a->delta_rep, 0, a->delta_words * a->n_rep * 8) != hipSuccess) return fail(RL_E_HIP, "memset");
     }
     if (c.agent == RL_AGENT_TRACES) {
-        if (a->S > 65535) return bad(fail(RL_E_ARG, "traces need S <= 65535"));
+        if (a->S > 65535) return fail(RL_E_ARG, "traces need S <= 65535");
         // shared mode: room for the pair layout (the selector / algorithm, and so
         // the layout, may change later: agent_select_kernel)
         const bool pairs = !a->priv;
-        if (pairs && SA > 32767) return bad(fail(RL_E_ARG, "shared-mode traces need S*A <= 32767"));
+        if (pairs && SA > 32767) return fail(RL_E_ARG, "shared-mode traces need S*A <= 32767");
         const size_t SL = (pairs ? SA : (size_t)a->S) * L;   // pair lists are S*A long
-        if ((rc = dalloc(&a->trace, SA * L)) || (rc = dalloc(&a->tlist, SL)) || (rc = dalloc(&a->slot_of, SL)) ||
-            (rc = dalloc(&a->tcnt, L)))
-            return bad(rc);
+        if ((rc = a->trace.alloc(SA * L)) || (rc = a->tlist.alloc(SL)) || (rc = a->slot_of.alloc(SL)) ||
+            (rc = a->tcnt.alloc(L)))
+            return rc;
         if (hipMemset(a->trace, 0, SA * L * 8) != hipSuccess || hipMemset(a->tlist, 0, SL * 2) != hipSuccess ||
             hipMemset(a->slot_of, 0, SL * 2) != hipSuccess || hipMemset(a->tcnt, 0, (size_t)L * 4) != hipSuccess)
-            return bad(fail(RL_E_HIP, "memset"));
+            return fail(RL_E_HIP, "memset");
         if (pairs) {
             a->vbits_words = (size_t)((a->S + 31) / 32) * L;
-            if ((rc = dalloc(&a->vbits, a->vbits_words))) return bad(rc);
-            if (hipMemset(a->vbits, 0, a->vbits_words * 4) != hipSuccess) return bad(fail(RL_E_HIP, "memset"));
+            if ((rc = a->vbits.alloc(a->vbits_words))) return rc;
+            if (hipMemset(a->vbits, 0, a->vbits_words * 4) != hipSuccess) return fail(RL_E_HIP, "memset");
         }
     }
-    if (!a->eh.trans.empty() &&
-        hipMemcpy(a->trans, a->eh.trans.data(), a->eh.trans.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-        return bad(fail(RL_E_HIP, "table upload"));
-    if (!a->eh.dev_cdf().empty() &&
-        hipMemcpy(a->cdf, a->eh.dev_cdf().data(), a->eh.dev_cdf().size() * 8, hipMemcpyHostToDevice) != hipSuccess)
-        return bad(fail(RL_E_HIP, "table upload"));
-    if (hipMemset(a->stats_d, 0, STATS_W * 8 * STATS_REP) != hipSuccess) return bad(fail(RL_E_HIP, "memset"));
-    if ((rc = dalloc(&a->ctl_d, 3))) return bad(rc);
-    if (hipHostMalloc((void **)&a->ctl_h, 6 * 8, hipHostMallocDefault) != hipSuccess ||
-        hipEventCreateWithFlags(&a->ctl_ev[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&a->ctl_ev[1], hipEventDisableTiming) != hipSuccess)
-        return bad(fail(RL_E_HIP, "loop control buffers"));
+    if (hipMemset(a->stats_d, 0, STATS_W * 8 * STATS_REP) != hipSuccess) return fail(RL_E_HIP, "memset");
+    if ((rc = agent_ctl_setup(a))) return rc;
 
     KParams &p = a->kp;
-    p.L = a->L; p.G = a->G; p.K = a->K; p.S = a->S; p.A = a->A; p.P = a->P;
-    p.core = a->core; p.rng = a->rng; p.aux = a->aux; p.epi_reward = a->epi_reward;
-    p.q_base = a->q_base; p.n_base = a->n_base; p.t_base = a->t_base;
     p.delta = a->delta;
     p.delta_rep = a->delta_rep;
     p.n_rep = a->n_rep;
@@ -1848,21 +1376,13 @@ int rl_agent_create(const rl_agent_config *cfg, rl_agent **out) {
     p.net_w = a->net_w; p.feat = a->feat; p.n_in = a->n_in; p.n_hidden = c.net.hidden; p.n_params = a->n_params;
     p.act1 = c.net.act_hidden; p.act2 = c.net.act_out;
     p.trace = a->trace; p.tlist = a->tlist; p.slot_of = a->slot_of; p.tcnt = a->tcnt; p.vbits = a->vbits;
-    p.trans = a->trans; p.start_cdf = a->cdf; p.n_start = a->eh.dev_n_start();
-    p.fixed_start = a->eh.fixed_start;
-    p.slippery = a->eh.slippery;
-    p.max_steps = a->eh.max_steps; p.th1 = a->eh.th1; p.th2 = a->eh.th2; p.th3 = a->eh.th3;
-    p.trunc_reward = a->eh.trunc_reward;
-    p.target_episodes = 0; p.eval_at = 0; p.eval_div = 0; p.eval_episodes = c.eval_episodes; p.eval_only = 0;
-    p.stats = a->stats_d;
-    p.rec = nullptr;
     agent_sync_params(a);
-    if ((rc = agent_select_kernel(a))) return bad(rc);
+    if ((rc = agent_select_kernel(a))) return rc;
     launch_lane_init(c.env.kind, p, c.seed, c.lane_offset, c.eps0, a->stream);
-    if (hipGetLastError() != hipSuccess) return bad(fail(RL_E_HIP, "lane init launch"));
-    if ((rc = agent_reset_policy(a))) return bad(rc);
-    if ((rc = agent_reset_selector(a))) return bad(rc);
-    *out = a;
+    if (hipGetLastError() != hipSuccess) return fail(RL_E_HIP, "lane init launch");
+    if ((rc = agent_reset_policy(a))) return rc;
+    if ((rc = agent_reset_selector(a))) return rc;
+    *out = h.release();
     return RL_OK;
 }
 
@@ -1871,23 +1391,15 @@ void rl_agent_destroy(rl_agent *a) {
     (void)hipSetDevice(a->device);
     if (a->own_stream) (void)hipStreamSynchronize(a->own_stream);
     for (auto &ev : a->events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
-    dfree(a->core); dfree(a->rng); dfree(a->aux); dfree(a->epi_reward);
-    dfree(a->q_base); dfree(a->n_base); dfree(a->t_base); dfree(a->delta_own); dfree(a->qslot);
-    dfree(a->delta_rep);
-    dfree(a->q_priv); dfree(a->n_priv); dfree(a->t_priv);
-    dfree(a->trace); dfree(a->tlist); dfree(a->slot_of); dfree(a->tcnt); dfree(a->vbits); dfree(a->trans); dfree(a->cdf);
-    dfree(a->stats_d); dfree(a->rec_d); dfree(a->elog_d); dfree(a->elog_cnt_d);
-    dfree(a->mcnt); dfree(a->mrec); dfree(a->mslot);
-    peer_free(a);
-    dfree(a->net_w); dfree(a->feat); dfree(a->ctl_d); dfree(a->call_d);
-    dfree(a->members_d); dfree(a->pop_stats_d);
+    peer_detach(a);   // the peers' IPC mappings closed before the exchange region goes
     if (a->call_h) (void)hipHostFree(a->call_h);
     if (a->env_view) a->env_view->owner = nullptr;   // the view outlives its agent: calls fail with RL_E_STATE
     if (a->ctl_h) (void)hipHostFree(a->ctl_h);
     for (hipEvent_t e : a->ctl_ev)
         if (e) (void)hipEventDestroy(e);
-    if (a->own_stream) (void)hipStreamDestroy(a->own_stream);
-    delete a;
+    const hipStream_t stream = a->own_stream;
+    delete a;   // frees its device arrays
+    if (stream) (void)hipStreamDestroy(stream);
 }
 
 int rl_agent_set_future_q_value_func(rl_agent *a, int32_t algo) {
@@ -2004,6 +1516,17 @@ int rl_agent_synchronize(rl_agent *a) {
     return a->peer.on ? peer_check(a) : RL_OK;
 }
 
+// one row of STATS_W counters (rl_kparams.h) as rl_stats; `launches` is host-side
+static void stats_from_row(const unsigned long long *r, uint64_t launches, rl_stats *out) {
+    out->train_steps = r[0]; out->eval_steps = r[1]; out->train_episodes = r[2]; out->eval_episodes = r[3];
+    out->reward_sum_q16 = (int64_t)r[4];
+    out->done_lanes = r[5];
+    out->launches = launches;
+    out->trace_states = r[7];
+    out->q_clamp_hits = r[ACC_CLAMP];
+    out->delta_saturations = r[ACC_SAT];
+}
+
 int rl_agent_stats(rl_agent *a, rl_stats *out) {
     if (!a || !out) return fail(RL_E_ARG, "null argument");
     HIPC(hipSetDevice(a->device));
@@ -2013,16 +1536,7 @@ int rl_agent_stats(rl_agent *a, rl_stats *out) {
     unsigned long long s[STATS_W] = {};
     for (uint32_t r = 0; r < STATS_REP; ++r)
         for (uint32_t i = 0; i < STATS_W; ++i) s[i] += rep[r * STATS_W + i];
-    out->train_steps = s[0];
-    out->eval_steps = s[1];
-    out->train_episodes = s[2];
-    out->eval_episodes = s[3];
-    out->reward_sum_q16 = (int64_t)s[4];
-    out->done_lanes = s[5];
-    out->launches = a->launches;
-    out->trace_states = s[7];
-    out->q_clamp_hits = s[ACC_CLAMP];
-    out->delta_saturations = s[ACC_SAT];
+    stats_from_row(s, a->launches, out);
     return RL_OK;
 }
 
@@ -2068,15 +1582,7 @@ int rl_agent_get_q(rl_agent *a, double *out, size_t n) {
     const size_t PSA = (size_t)a->P * a->S * a->A;
     if (a->neural) {   // Policy::get_values of every state: [n_lanes][S][A]
         if (n < PSA * a->L) return fail(RL_E_ARG, "output too small: need n_lanes*S*A");
-        double *d = nullptr;
-        HIPC(hipMalloc(&d, PSA * a->L * 8));
-        launch_net_values(a->kp, d, a->stream);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(out, d, PSA * a->L * 8, hipMemcpyDeviceToHost, a->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(a->stream);
-        (void)hipFree(d);
-        HIPC(e);
-        return RL_OK;
+        return rl_agent_get_q_lanes(a, 0, a->L, out, n);   // the window of every lane
     }
     if (a->priv) {
         if (n < PSA * a->L) return fail(RL_E_ARG, "output too small: need n_lanes*P*S*A");
@@ -2233,33 +1739,21 @@ int rl_population_create(const rl_agent_config *base, const rl_member_config *me
         return fail(RL_E_ARG, "population: env.map8x8 must be a built-in map, 0 or 1 (registered and wide maps "
                               "are not supported)");
     rl_agent *a = new rl_agent();
-    a->cfg = c;
     a->pop = true;
     a->M = n_members;
     a->members.assign(members, members + n_members);
-    int rc = build_env(c.env, a->eh);
+    int rc = agent_host_init(a, c);
     if (rc) { delete a; return rc; }
-    auto bad = [&](int code) { rl_agent_destroy(a); return code; };
-    a->device = c.device;
-    a->S = a->eh.S; a->A = a->eh.A; a->P = c.policy == RL_POLICY_DOUBLE ? 2 : 1;
-    a->L = c.n_lanes; a->G = c.group_size; a->K = c.sync_every;
     a->n_groups = a->M;
     // the representation (q_default under every member's proof) and the LDS guard: host arithmetic
     a->q_abs0 = std::fabs(c.q_default) == std::fabs(c.q_default) ? std::fabs(c.q_default) : INFINITY;
     a->qrepr = (fix_proven(a) && fix_exact(c.q_default)) ? RL_QREPR_FIXED40 : RL_QREPR_F64;
     if ((rc = population_select_kernel(a))) { delete a; return rc; }
 
-    if (hipSetDevice(c.device) != hipSuccess) return bad(fail(RL_E_HIP, "hipSetDevice failed (no GPU?)"));
-    if (hipStreamCreateWithFlags(&a->own_stream, hipStreamNonBlocking) != hipSuccess)
-        return bad(fail(RL_E_HIP, "hipStreamCreate failed"));
-    a->stream = a->own_stream;
-    const size_t L = a->L, M = a->M, SA = (size_t)a->S * a->A, PSA = a->P * SA;
-    if ((rc = dalloc(&a->core, L)) || (rc = dalloc(&a->rng, L)) || (rc = dalloc(&a->aux, L)) ||
-        (rc = dalloc(&a->epi_reward, L)) || (rc = dalloc(&a->stats_d, STATS_W * STATS_REP)) ||
-        (rc = dalloc(&a->trans, a->eh.trans.size())) || (rc = dalloc(&a->cdf, a->eh.dev_cdf().size())) ||
-        (rc = dalloc(&a->q_base, M * PSA)) || (rc = dalloc(&a->n_base, M * SA)) || (rc = dalloc(&a->t_base, M)) ||
-        (rc = dalloc(&a->members_d, M)) || (rc = dalloc(&a->pop_stats_d, M * STATS_W)) || (rc = dalloc(&a->ctl_d, 3)))
-        return bad(rc);
+    std::unique_ptr<rl_agent, decltype(&rl_agent_destroy)> h(a, rl_agent_destroy);   // a later failure destroys it
+    if ((rc = agent_device_setup(a, a->M))) return rc;   // one table per member
+    const size_t M = a->M;
+    if ((rc = a->members_d.alloc(M)) || (rc = a->pop_stats_d.alloc(M * STATS_W)) || (rc = agent_ctl_setup(a))) return rc;
     std::vector<MemberParams> mp(M);
     for (size_t m = 0; m < M; ++m) {
         const rl_member_config &mc = a->members[m];
@@ -2270,41 +1764,20 @@ int rl_population_create(const rl_agent_config *base, const rl_member_config *me
     if (hipMemcpy(a->members_d, mp.data(), M * sizeof(MemberParams), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemset(a->pop_stats_d, 0, M * STATS_W * 8) != hipSuccess ||
         hipMemset(a->stats_d, 0, STATS_W * 8 * STATS_REP) != hipSuccess)
-        return bad(fail(RL_E_HIP, "member table upload"));
-    if (!a->eh.trans.empty() &&
-        hipMemcpy(a->trans, a->eh.trans.data(), a->eh.trans.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-        return bad(fail(RL_E_HIP, "table upload"));
-    if (!a->eh.dev_cdf().empty() &&
-        hipMemcpy(a->cdf, a->eh.dev_cdf().data(), a->eh.dev_cdf().size() * 8, hipMemcpyHostToDevice) != hipSuccess)
-        return bad(fail(RL_E_HIP, "table upload"));
-    if (hipHostMalloc((void **)&a->ctl_h, 6 * 8, hipHostMallocDefault) != hipSuccess ||
-        hipEventCreateWithFlags(&a->ctl_ev[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&a->ctl_ev[1], hipEventDisableTiming) != hipSuccess)
-        return bad(fail(RL_E_HIP, "loop control buffers"));
+        return fail(RL_E_HIP, "member table upload");
 
     KParams &p = a->kp;
-    p.L = a->L; p.G = a->G; p.K = a->K; p.S = a->S; p.A = a->A; p.P = a->P;
-    p.core = a->core; p.rng = a->rng; p.aux = a->aux; p.epi_reward = a->epi_reward;
-    p.q_base = a->q_base; p.n_base = a->n_base; p.t_base = a->t_base;   // member 0's; each block takes its own
     p.n_rep = 1;
     p.n_groups = a->M;
-    p.trans = a->trans; p.start_cdf = a->cdf; p.n_start = a->eh.dev_n_start();
-    p.fixed_start = a->eh.fixed_start;
-    p.slippery = a->eh.slippery;
-    p.max_steps = a->eh.max_steps; p.th1 = a->eh.th1; p.th2 = a->eh.th2; p.th3 = a->eh.th3;
-    p.trunc_reward = a->eh.trunc_reward;
-    p.target_episodes = 0; p.eval_at = 0; p.eval_div = 0; p.eval_episodes = c.eval_episodes; p.eval_only = 0;
-    p.stats = a->stats_d;
-    p.rec = nullptr;
     agent_sync_params(a);
     for (uint32_t m = 0; m < a->M; ++m) {   // member m's lanes draw from (seed_m, lane_offset_m + i)
         const rl_member_config &mc = a->members[m];
         launch_lane_init(c.env.kind, member_lanes(a, m), mc.seed, mc.lane_offset, mc.eps0, a->stream);
     }
-    if (hipGetLastError() != hipSuccess) return bad(fail(RL_E_HIP, "lane init launch"));
-    if ((rc = agent_reset_policy(a))) return bad(rc);
-    if ((rc = agent_reset_selector(a))) return bad(rc);
-    *out = a;
+    if (hipGetLastError() != hipSuccess) return fail(RL_E_HIP, "lane init launch");
+    if ((rc = agent_reset_policy(a))) return rc;
+    if ((rc = agent_reset_selector(a))) return rc;
+    *out = h.release();
     return RL_OK;
 }
 
@@ -2379,17 +1852,7 @@ int rl_population_stats(rl_agent *a, uint32_t m0, uint32_t n, rl_stats *out) {
     HIPC(hipMemcpyAsync(s.data(), a->pop_stats_d + (size_t)m0 * STATS_W, s.size() * 8, hipMemcpyDeviceToHost,
                         a->stream));
     HIPC(hipStreamSynchronize(a->stream));
-    for (uint32_t m = 0; m < n; ++m) {
-        const unsigned long long *r = &s[(size_t)m * STATS_W];
-        rl_stats &o = out[m];
-        o.train_steps = r[0]; o.eval_steps = r[1]; o.train_episodes = r[2]; o.eval_episodes = r[3];
-        o.reward_sum_q16 = (int64_t)r[4];
-        o.done_lanes = r[5];
-        o.launches = a->launches;
-        o.trace_states = r[7];
-        o.q_clamp_hits = r[ACC_CLAMP];
-        o.delta_saturations = r[ACC_SAT];
-    }
+    for (uint32_t m = 0; m < n; ++m) stats_from_row(&s[(size_t)m * STATS_W], a->launches, &out[m]);
     return RL_OK;
 }
 
@@ -2421,7 +1884,7 @@ int agent_call(rl_agent *a, int op, uint32_t lane0, uint32_t n, const uint64_t *
     HIPC(hipSetDevice(a->device));
     if (!a->call_d) {   // sized for every lane; a call stages only its n entries
         const CallLayout full(a->L);
-        if (int rc = dalloc(&a->call_d, full.total)) return rc;
+        if (int rc = a->call_d.alloc(full.total)) return rc;
         HIPC(hipHostMalloc((void **)&a->call_h, full.total, hipHostMallocDefault));
     }
     const CallLayout cl(n);   // compact: a one-lane call moves a few bytes, not O(L)
@@ -2507,7 +1970,8 @@ int rl_agent_env(rl_agent *a, rl_env **out) {
     *out = nullptr;
     if (a->env_view) return fail(RL_E_STATE, "this agent already has an Env view (rl_env_destroy it first)");
     HIPC(hipSetDevice(a->device));
-    rl_env *e = new rl_env();
+    std::unique_ptr<rl_env, decltype(&rl_env_destroy)> h(new rl_env(), rl_env_destroy);
+    rl_env *e = h.get();
     e->cfg = a->cfg.env;
     e->eh = a->eh;
     e->device = a->device;
@@ -2515,22 +1979,15 @@ int rl_agent_env(rl_agent *a, rl_env **out) {
     e->owner = a;
     e->L = a->L;
     int rc;
-    if ((rc = dalloc(&e->act_d, e->L)) || (rc = dalloc(&e->obs_d, e->L)) || (rc = dalloc(&e->rew_d, e->L)) ||
-        (rc = dalloc(&e->term_d, e->L))) {
-        rl_env_destroy(e);
+    if ((rc = e->act_d.alloc(e->L)) || (rc = e->obs_d.alloc(e->L)) || (rc = e->rew_d.alloc(e->L)) ||
+        (rc = e->term_d.alloc(e->L)))
         return rc;
-    }
-    e->core = a->core; e->rng = a->rng; e->trans = a->trans; e->cdf = a->cdf;
     KParams &p = e->kp;
     p.L = e->L; p.S = a->S; p.A = a->A; p.P = 1;
     p.core = a->core; p.rng = a->rng;
-    p.trans = a->trans; p.start_cdf = a->cdf; p.n_start = a->eh.dev_n_start();
-    p.fixed_start = a->eh.fixed_start;
-    p.slippery = a->eh.slippery;
-    p.max_steps = a->eh.max_steps; p.th1 = a->eh.th1; p.th2 = a->eh.th2; p.th3 = a->eh.th3;
-    p.trunc_reward = a->eh.trunc_reward;
+    a->tables.params(a->eh, p);
     e->ready.assign(e->L, 0);
-    a->env_view = e;
+    a->env_view = h.release();
     *out = e;
     return RL_OK;
 }
@@ -2540,7 +1997,7 @@ int rl_agent_set_recording(rl_agent *a, int32_t enable) {
     if (!a) return fail(RL_E_ARG, "null agent");
     HIPC(hipSetDevice(a->device));
     if (enable && !a->rec_d) {
-        int rc = dalloc(&a->rec_d, (size_t)a->K * a->L);
+        int rc = a->rec_d.alloc((size_t)a->K * a->L);
         if (rc) return rc;
     }
     a->recording = enable != 0;
@@ -2572,14 +2029,12 @@ int rl_agent_set_planning(rl_agent *a, uint32_t planning_steps) {
     if (planning_steps && !a->priv) return fail(RL_E_ARG, "Dyna planning needs group_size 1 (private agents)");
     HIPC(hipSetDevice(a->device));
     HIPC(hipStreamSynchronize(a->stream));
-    dfree(a->mcnt); dfree(a->mrec); dfree(a->mslot);
-    a->mcnt = a->mslot = nullptr;
-    a->mrec = nullptr;
+    a->mcnt.reset(); a->mrec.reset(); a->mslot.reset();
     a->plan = 0;
     if (planning_steps) {
         const size_t n = (size_t)a->S * a->A * a->L;
         int rc;
-        if ((rc = dalloc(&a->mcnt, a->L)) || (rc = dalloc(&a->mrec, n)) || (rc = dalloc(&a->mslot, n)))
+        if ((rc = a->mcnt.alloc(a->L)) || (rc = a->mrec.alloc(n)) || (rc = a->mslot.alloc(n)))
             return rc;
         HIPC(hipMemset(a->mcnt, 0, (size_t)a->L * 4));
         HIPC(hipMemset(a->mslot, 0, n * 4));
@@ -2594,14 +2049,12 @@ int rl_agent_set_episode_log(rl_agent *a, uint32_t capacity_per_lane) {
     if (!a) return fail(RL_E_ARG, "null agent");
     HIPC(hipSetDevice(a->device));
     HIPC(hipStreamSynchronize(a->stream));
-    dfree(a->elog_d);
-    dfree(a->elog_cnt_d);
-    a->elog_d = nullptr;
-    a->elog_cnt_d = nullptr;
+    a->elog_d.reset();
+    a->elog_cnt_d.reset();
     a->elog_cap = 0;
     if (capacity_per_lane) {
         int rc;
-        if ((rc = dalloc(&a->elog_d, (size_t)capacity_per_lane * a->L)) || (rc = dalloc(&a->elog_cnt_d, a->L)))
+        if ((rc = a->elog_d.alloc((size_t)capacity_per_lane * a->L)) || (rc = a->elog_cnt_d.alloc(a->L)))
             return rc;
         HIPC(hipMemset(a->elog_cnt_d, 0, (size_t)a->L * 4));
         a->elog_cap = capacity_per_lane;
@@ -2873,12 +2326,12 @@ int peer_alloc(rl_agent *a) {
     if (int rc = rl_agent_delta_cap_words(a, &cap)) return rc;
     pm.cap = std::max<uint64_t>(cap, 16);
     const size_t bytes = (2 * pm.cap + 32) * 8;
-    if (hipExtMallocWithFlags((void **)&pm.region, bytes, hipDeviceMallocUncached) != hipSuccess) {
-        pm.region = nullptr;
+    int64_t *region = nullptr;
+    if (hipExtMallocWithFlags((void **)&region, bytes, hipDeviceMallocUncached) != hipSuccess)
         return fail(RL_E_OOM, "peer exchange region (uncached)");
-    }
+    pm.region.reset(region, bytes / 8);
     HIPC(hipMemset(pm.region, 0, bytes));
-    if (hipMalloc((void **)&pm.err_d, 4) != hipSuccess) return fail(RL_E_OOM, "peer error word");
+    if (pm.err_d.alloc(1) != RL_OK) return fail(RL_E_OOM, "peer error word");
     HIPC(hipMemset(pm.err_d, 0, 4));
     int khz = 100000;   // the wall clock (s_memrealtime) rate
     (void)hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, a->device);
@@ -2892,18 +2345,10 @@ void peer_detach(rl_agent *a) {
     for (int32_t r = 0; r < (int32_t)pm.bases.size(); ++r)
         if (r != pm.rank && pm.bases[r]) (void)hipIpcCloseMemHandle(pm.bases[r]);
     pm.bases.clear();
-    if (pm.bases_d) (void)hipFree(pm.bases_d);
-    pm.bases_d = nullptr;
+    pm.bases_d.reset();
     pm.on = false;
     pm.epoch = 0;
     if (pm.region) (void)hipMemset(pm.region, 0, (2 * pm.cap + 32) * 8);   // flags back to epoch 0
-}
-void peer_free(rl_agent *a) {
-    peer_detach(a);
-    if (a->peer.region) (void)hipFree(a->peer.region);
-    if (a->peer.err_d) (void)hipFree(a->peer.err_d);
-    a->peer.region = nullptr;
-    a->peer.err_d = nullptr;
 }
 // a peer wait that timed out (a rank that never reached the merge)
 int peer_check(rl_agent *a) {
@@ -2984,8 +2429,7 @@ int rl_agent_peer_attach(rl_agent *a, int32_t rank, int32_t world, const void *h
         }
         pm.bases[r] = (int64_t *)p;
     }
-    if (hipMalloc((void **)&pm.bases_d, world * sizeof(int64_t *)) != hipSuccess ||
-        hipMemcpy(pm.bases_d, pm.bases.data(), world * sizeof(int64_t *), hipMemcpyHostToDevice) != hipSuccess) {
+    if (pm.bases_d.alloc((size_t)world) != RL_OK || pm.bases_d.fill(pm.bases.data(), "peer table") != RL_OK) {
         peer_detach(a);
         return fail(RL_E_HIP, "peer table");
     }

@@ -18,7 +18,7 @@ for m in "$@"; do
   objs="exp/tu_$m.o"
   for t in $ALL; do [ "$t" = "$TU" ] || objs="$objs build/rl_train_$t.hip.o"; done
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o exp/librlamd_$m.so $objs \
-     build/rl_misc.hip.o build/rl_host.cpp.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+     build/rl_misc.hip.o build/rl_host*.cpp.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 done
 rm -f exp/*.o
 ls -la exp
