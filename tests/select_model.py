@@ -72,8 +72,10 @@ carried across launches by the Predictor.
 Outside the model
 -----------------
 ln(t) (a checked input), the train() evaluate interleave (plain run() launches in
-RL_MODE_TRAIN only: every record has mode 0), private mode, the neural policy and
-populations.
+RL_MODE_TRAIN only: every record has mode 0) and populations.  Private mode, Dyna-Q
+planning and the neural policy are outside this file too, but no longer unpinned:
+tests/private_model.py reuses the stream, the card rule, the envs and the selection
+helpers here and predicts a private lane's records, values, counters and epsilon.
 
 Mutations
 ---------

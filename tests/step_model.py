@@ -117,9 +117,11 @@ td_source="record" stay as they were.
 Outside the model
 -----------------
 ln(t) (a checked input); the train() evaluate interleave (plain run() launches
-in RL_MODE_TRAIN only); private mode (group_size 1); the neural policy;
-populations.  Without a predictor also the RNG, the envs and the selections
-themselves (records are the input).
+in RL_MODE_TRAIN only); populations.  Private mode (group_size 1), Dyna-Q
+planning and the neural policy are outside THIS model and have one of their own:
+tests/private_model.py predicts a private lane from the seed the same way.
+Without a predictor also the RNG, the envs and the selections themselves
+(records are the input).
 """
 import math
 import struct
