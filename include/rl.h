@@ -419,14 +419,16 @@ int rl_agent_lane_state(rl_agent *a, uint32_t *core, uint32_t *aux, size_t n_lan
  * done earlier is still launched, idle: nothing of it moves.
  * Limits (v1): 2 <= G <= 1024, M >= 1, M * G < 2^32; the one-step agent; tabular or
  * double policy; eps-greedy or UCB; SARSA, Q-learning or expected SARSA, but not UCB
- * with expected SARSA; FrozenLake on the built-in maps (0 / 1), CliffWalking, Taxi,
- * Blackjack.  A learner group whose tables exceed the LDS is rejected as by
- * rl_agent_create (Blackjack with the double policy under UCB).
+ * with expected SARSA.  rl_population_create: FrozenLake on the built-in maps (0 / 1),
+ * CliffWalking, Taxi, Blackjack, one env for all members.  rl_population_create_maps:
+ * FrozenLake or FrozenLakeEdited with one map per member (below).  A learner group
+ * whose tables exceed the LDS is rejected as by rl_agent_create (Blackjack with the
+ * double policy under UCB; large wide maps).
  * Errors: RL_E_ARG with a message naming the field, before any HIP call, for
  * n_members == 0, G outside 2..1024, n_lanes != M * G, a combination outside the limits
- * (traces, NeuralPolicy, FrozenLakeEdited, registered or wide maps, UCB + expected
- * SARSA), a member window with m0 + n > M, a buffer length other than the stated one, a
- * null pointer.
+ * (traces, NeuralPolicy, UCB + expected SARSA; for rl_population_create FrozenLakeEdited
+ * and registered or wide maps), a member window with m0 + n > M, a buffer length other
+ * than the stated one, a null pointer.
  * The handle is an rl_agent.  rl_agent_destroy, _run, _synchronize, _train, _evaluate,
  * _reset (every member back to q_default and its own fresh selector), _stats (totals
  * over the members), _dims, _q_repr, _set_q_mode, _get_epsilon, _lane_state (M * G
@@ -445,6 +447,26 @@ typedef struct rl_member_config {
  * (lr .. ucb_c, seed, lane_offset) and lambda / net are ignored */
 int rl_population_create(const rl_agent_config *base, const rl_member_config *members,
                          uint32_t n_members, rl_agent **out);
+/* rl_population_create with FrozenLake / FrozenLakeEdited maps of the caller's own,
+ * one per member: map_ids[m] is member m's map (rl_map_register / rl_map_register_wide
+ * ids; 0 and 1 are the built-ins and count as narrow-format maps; an id may repeat, and
+ * members on one map share its device table).  Member m is, bit for bit, the agent
+ * rl_agent_create builds alone from `base` with env.map8x8 = map_ids[m], n_lanes =
+ * group_size = G and member m's fields; the population is in the fixed point iff every
+ * member's lone agent on its own map would be.  base->env.kind is FrozenLake or
+ * FrozenLakeEdited, base->env.slippery and max_steps are shared by the members and
+ * base->env.map8x8 is ignored.  All maps have the same number of rows and of columns
+ * and one table format (rl_map_is_wide equal for all); the other limits are
+ * rl_population_create's.  Errors (RL_E_ARG, before any HIP call): map_ids null, an
+ * unknown id (the member is named), maps of different dimensions (both members and
+ * shapes are named), mixed table formats, another env kind.
+ * Out of scope: per-member slippery / max_steps, maps of different sizes. */
+int rl_population_create_maps(const rl_agent_config *base, const rl_member_config *members,
+                              const int32_t *map_ids, uint32_t n_members, rl_agent **out);
+/* members [m0, m0 + n): their map ids; n_out must be n.  A built-in-map population of
+ * rl_population_create gives the shared id for every member; RL_E_STATE on a
+ * population of another env */
+int rl_population_maps(rl_agent *a, uint32_t m0, uint32_t n, int32_t *map_ids, size_t n_out);
 int rl_population_size(rl_agent *a, uint32_t *n_members, uint32_t *lanes_per_member);
 /* members [m0, m0 + n): [member][P][S][A] values / raw words (rl_agent_get_q_raw);
  * n_out must be n * P*S*A */

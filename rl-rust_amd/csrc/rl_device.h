@@ -653,7 +653,7 @@ __device__ __forceinline__ void fl_advance(bool doR, bool doS, uint32_t &pos, ui
     uint32_t i = 0, s0 = 0;
     if constexpr (MAPS) {
         const bool slip = SLIP == 1 || (SLIP < 0 && t.slippery);
-        const bool drawn = t.fixed_start < 0;          // uniform over the launch
+        const bool drawn = t.fixed_start < 0;          // uniform over the block
         s0 = drawn ? 0u : (uint32_t)t.fixed_start;
         if ((slip && st) || (drawn && doR)) {
             const double u = uniform01(r);
@@ -789,7 +789,7 @@ __device__ __forceinline__ void fl_advance_wide(bool doR, bool doS, uint32_t &po
     const bool trunc = doS && z >= t.max_steps;
     const bool st = doS && !trunc;
     const bool slip = SLIP == 1 || (SLIP < 0 && t.slippery);
-    const bool drawn = t.fixed_start < 0;              // uniform over the launch
+    const bool drawn = t.fixed_start < 0;              // uniform over the block
     uint32_t d = a, s0 = drawn ? 0u : (uint32_t)t.fixed_start;
     if ((slip && st) || (drawn && doR)) {
         const double u = uniform01(r);

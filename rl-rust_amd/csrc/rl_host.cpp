@@ -308,6 +308,19 @@ struct rl_agent {
     DevBuf<unsigned long long> pop_stats_d;   // [M][STATS_W]
     pop_launch_fn pop_fn = nullptr;
     PopParams pp{};
+    // ... on the members' own maps (rl_population_create_maps): one EnvHost and one
+    // device table per DISTINCT id, in the map kernels' form; `eh` / `tables` are the
+    // first member's map, map_eh / map_tables the further ones in order of first use;
+    // member m runs map map_of[m].  The LDS carve takes the largest start list.
+    bool pop_maps = false;
+    std::vector<int32_t> map_ids;     // [M]
+    std::vector<uint32_t> map_of;     // [M]: 0 = eh, d >= 1 = map_eh[d - 1]
+    std::vector<EnvHost> map_eh;
+    std::vector<EnvTables> map_tables;
+    uint32_t carve_n_start = 0;
+    DevBuf<MemberEnv> member_envs_d;  // [M]
+    pop_maps_launch_fn pop_maps_fn = nullptr;
+    PopMapParams pm{};
 };
 
 namespace {
@@ -342,8 +355,14 @@ size_t table_count(const rl_agent *a) { return a->pop ? a->M : 1; }
 // slots) as shared_smem_bytes or shared_pair_cap reports it: the one place that spells their argument list
 template <class Of>
 auto shared_carve(const rl_agent *a, Of of, uint32_t nthr, uint32_t trc_kb) {
-    return of(a->eh.kenv, a->cfg.agent, a->cfg.policy, a->cfg.selector, a->cfg.algo, a->S, a->A, a->eh.dev_n_start(),
-              nthr, trc_kb, a->qrepr == RL_QREPR_F64, a->kp.ucb_pack);
+    return of(a->eh.kenv, a->cfg.agent, a->cfg.policy, a->cfg.selector, a->cfg.algo, a->S, a->A,
+              a->pop_maps ? a->carve_n_start : a->eh.dev_n_start(), nthr, trc_kb, a->qrepr == RL_QREPR_F64,
+              a->kp.ucb_pack);
+}
+// a population's train kernel: the launch, or with occ its resident workgroups per CU
+hipError_t population_launch(rl_agent *a, int *occ) {
+    return a->pop_maps ? a->pop_maps_fn(a->kp, a->pp, a->pm, a->grid, a->block, a->smem, a->stream, occ)
+                       : a->pop_fn(a->kp, a->pp, a->grid, a->block, a->smem, a->stream, occ);
 }
 
 // An experiment override: the integer in the variable `name` where `allowed` takes
@@ -361,8 +380,10 @@ int env_override(const char *name, int dflt, Allowed allowed) {
 // engages below 1024 lanes).  Host arithmetic only, so rl_population_create runs the
 // LDS guard before its first HIP call.
 int population_select_kernel(rl_agent *a) {
-    a->pop_fn = lookup_population(a->eh.kenv, a->cfg.policy, a->cfg.selector, a->cfg.algo);
-    if (!a->pop_fn) return fail(RL_E_ARG, "no population kernel for this (env, policy, selector, algo)");
+    if (a->pop_maps) a->pop_maps_fn = lookup_population_maps(a->eh.kenv, a->cfg.policy, a->cfg.selector, a->cfg.algo);
+    else a->pop_fn = lookup_population(a->eh.kenv, a->cfg.policy, a->cfg.selector, a->cfg.algo);
+    if (a->pop_maps ? !a->pop_maps_fn : !a->pop_fn)
+        return fail(RL_E_ARG, "no population kernel for this (env, policy, selector, algo)");
     a->kp.ucb_pack = 0;
     a->kp.lpw = 64;
     a->kp.trc_kb = 0;
@@ -859,7 +880,7 @@ int launch_train_kernel(rl_agent *a, bool *merge = nullptr) {
         HIPC(hipEventRecord(e0, a->stream));
     }
     {
-        const hipError_t le = a->pop ? a->pop_fn(a->kp, a->pp, a->grid, a->block, a->smem, a->stream, nullptr)
+        const hipError_t le = a->pop ? population_launch(a, nullptr)
                                      : a->fn(a->kp, a->grid, a->block, a->smem, a->stream, nullptr);
         if (le != hipSuccess)
             return fail(RL_E_HIP, std::string("train kernel launch (smem ") + std::to_string(a->smem) +
@@ -1706,10 +1727,82 @@ int rl_agent_get_epsilon(rl_agent *a, double *out, size_t n) {
 // ---------------------------------------------------------------- population
 // M independent shared-Q agents of G lanes behind one handle and one launch
 // (rl.h).  Every argument is checked before the first HIP call.
-int rl_population_create(const rl_agent_config *base, const rl_member_config *members, uint32_t n_members,
-                         rl_agent **out) {
+
+// rl_population_create_maps' agent_host_init: every member's map checked (known id, one
+// shape, one table format) and one EnvHost built per distinct id, in the map kernels'
+// form (ids 0 / 1 as narrow maps with the fixed start 0).  Host arithmetic only.
+static int population_maps_host_init(rl_agent *a, const rl_agent_config &c, const int32_t *map_ids) {
+    a->cfg = c;
+    a->pop_maps = true;
+    a->map_ids.assign(map_ids, map_ids + a->M);
+    a->map_of.assign(a->M, 0);
+    std::vector<int32_t> distinct;        // ids in order of first use
+    std::vector<uint32_t> first_member;   // ... and the member that brought each
+    int32_t wide0 = 0;
+    for (uint32_t m = 0; m < a->M; ++m) {
+        const int32_t id = map_ids[m];
+        const auto it = std::find(distinct.begin(), distinct.end(), id);
+        if (it != distinct.end()) { a->map_of[m] = (uint32_t)(it - distinct.begin()); continue; }
+        int32_t wide = 0;
+        if (rl_map_is_wide(id, &wide) != RL_OK)
+            return fail(RL_E_ARG, "population: map_ids[" + std::to_string(m) + "] = " + std::to_string(id) +
+                                      " is not a known FrozenLake map id (0 = MAP_4X4, 1 = MAP_8X8, else an id from "
+                                      "rl_map_register / rl_map_register_wide)");
+        if (distinct.empty()) wide0 = wide;
+        else if (wide != wide0)
+            return fail(RL_E_ARG, "population: map_ids mixes table formats: member " + std::to_string(first_member[0]) +
+                                      "'s map is " + (wide0 ? "wide" : "narrow") + ", member " + std::to_string(m) +
+                                      "'s is " + (wide ? "wide" : "narrow") + " (rl_map_is_wide must be equal for all; "
+                                      "ids 0 / 1 are narrow)");
+        rl_env_config ec = c.env;
+        ec.map8x8 = id;
+        EnvHost e;
+        if (int rc = build_env(ec, e, true)) return rc;
+        const EnvHost &e0 = distinct.empty() ? e : a->eh;
+        if (e.nrow != e0.nrow || e.ncol != e0.ncol)
+            return fail(RL_E_ARG, "population: map_ids name maps of different dimensions: member " +
+                                      std::to_string(first_member[0]) + "'s map is " + std::to_string(e0.nrow) + "x" +
+                                      std::to_string(e0.ncol) + ", member " + std::to_string(m) + "'s is " +
+                                      std::to_string(e.nrow) + "x" + std::to_string(e.ncol));
+        a->map_of[m] = (uint32_t)distinct.size();
+        a->carve_n_start = std::max(a->carve_n_start, e.dev_n_start());
+        if (distinct.empty()) a->eh = std::move(e);
+        else a->map_eh.push_back(std::move(e));
+        distinct.push_back(id);
+        first_member.push_back(m);
+    }
+    a->cfg.env.map8x8 = map_ids[0];
+    a->device = c.device;
+    a->S = a->eh.S; a->A = a->eh.A; a->P = c.policy == RL_POLICY_DOUBLE ? 2 : 1;
+    a->L = c.n_lanes; a->G = c.group_size; a->K = c.sync_every;
+    return RL_OK;
+}
+// ... and its device part: the further maps' tables (the first went up with the
+// handle's own, agent_ctl_setup) and the members' env records
+static int population_maps_upload(rl_agent *a) {
+    int rc;
+    a->map_tables.resize(a->map_eh.size());
+    for (size_t d = 0; d < a->map_eh.size(); ++d)
+        if ((rc = a->map_tables[d].alloc(a->map_eh[d])) || (rc = a->map_tables[d].upload(a->map_eh[d]))) return rc;
+    std::vector<MemberEnv> me(a->M);
+    for (uint32_t m = 0; m < a->M; ++m) {
+        const uint32_t d = a->map_of[m];
+        const EnvHost &e = d ? a->map_eh[d - 1] : a->eh;
+        const EnvTables &t = d ? a->map_tables[d - 1] : a->tables;
+        me[m] = MemberEnv{t.trans, t.cdf, e.dev_n_start(), e.fixed_start};
+    }
+    if ((rc = a->member_envs_d.alloc(a->M)) || (rc = a->member_envs_d.fill(me.data(), "member env upload"))) return rc;
+    a->pm = PopMapParams{a->member_envs_d, a->carve_n_start, 0u};
+    return RL_OK;
+}
+
+// map_ids: null for rl_population_create (one env for all), else member m's map
+// (rl_population_create_maps)
+static int population_create(const rl_agent_config *base, const rl_member_config *members, const int32_t *map_ids,
+                             bool maps, uint32_t n_members, rl_agent **out) {
     if (!base) return fail(RL_E_ARG, "population: base is null");
     if (!members) return fail(RL_E_ARG, "population: members is null");
+    if (maps && !map_ids) return fail(RL_E_ARG, "population: map_ids is null");
     if (!out) return fail(RL_E_ARG, "population: out is null");
     *out = nullptr;
     const rl_agent_config &c = *base;
@@ -1732,17 +1825,20 @@ int rl_population_create(const rl_agent_config *base, const rl_member_config *me
         return fail(RL_E_ARG, "population: policy must be tabular or double (NeuralPolicy is not supported)");
     if (c.selector == RL_SEL_UCB && c.algo == RL_ALGO_EXPECTED_SARSA)
         return fail(RL_E_ARG, "population: selector UCB with algo expected SARSA is not supported");
-    if (c.env.kind < RL_ENV_FROZEN_LAKE || c.env.kind > RL_ENV_BLACKJACK)
+    if (maps && c.env.kind != RL_ENV_FROZEN_LAKE && c.env.kind != RL_ENV_FROZEN_LAKE_EDITED)
+        return fail(RL_E_ARG, "population: env.kind must be FrozenLake or FrozenLakeEdited for maps per member "
+                              "(the other envs have no caller-supplied form: use rl_population_create)");
+    if (!maps && (c.env.kind < RL_ENV_FROZEN_LAKE || c.env.kind > RL_ENV_BLACKJACK))
         return fail(RL_E_ARG, "population: env.kind must be FrozenLake, CliffWalking, Taxi or Blackjack "
                               "(FrozenLakeEdited is not supported)");
-    if (c.env.kind == RL_ENV_FROZEN_LAKE && c.env.map8x8 != 0 && c.env.map8x8 != 1)
+    if (!maps && c.env.kind == RL_ENV_FROZEN_LAKE && c.env.map8x8 != 0 && c.env.map8x8 != 1)
         return fail(RL_E_ARG, "population: env.map8x8 must be a built-in map, 0 or 1 (registered and wide maps "
                               "are not supported)");
     rl_agent *a = new rl_agent();
     a->pop = true;
     a->M = n_members;
     a->members.assign(members, members + n_members);
-    int rc = agent_host_init(a, c);
+    int rc = maps ? population_maps_host_init(a, c, map_ids) : agent_host_init(a, c);
     if (rc) { delete a; return rc; }
     a->n_groups = a->M;
     // the representation (q_default under every member's proof) and the LDS guard: host arithmetic
@@ -1754,6 +1850,7 @@ int rl_population_create(const rl_agent_config *base, const rl_member_config *me
     if ((rc = agent_device_setup(a, a->M))) return rc;   // one table per member
     const size_t M = a->M;
     if ((rc = a->members_d.alloc(M)) || (rc = a->pop_stats_d.alloc(M * STATS_W)) || (rc = agent_ctl_setup(a))) return rc;
+    if (a->pop_maps && (rc = population_maps_upload(a))) return rc;
     std::vector<MemberParams> mp(M);
     for (size_t m = 0; m < M; ++m) {
         const rl_member_config &mc = a->members[m];
@@ -1781,6 +1878,16 @@ int rl_population_create(const rl_agent_config *base, const rl_member_config *me
     return RL_OK;
 }
 
+int rl_population_create(const rl_agent_config *base, const rl_member_config *members, uint32_t n_members,
+                         rl_agent **out) {
+    return population_create(base, members, nullptr, false, n_members, out);
+}
+
+int rl_population_create_maps(const rl_agent_config *base, const rl_member_config *members, const int32_t *map_ids,
+                              uint32_t n_members, rl_agent **out) {
+    return population_create(base, members, map_ids, true, n_members, out);
+}
+
 namespace {
 int population_window(rl_agent *a, uint32_t m0, uint32_t n, const char *call) {
     if (!a) return fail(RL_E_ARG, std::string(call) + ": null handle");
@@ -1797,6 +1904,17 @@ int rl_population_size(rl_agent *a, uint32_t *n_members, uint32_t *lanes_per_mem
     if (int rc = population_window(a, 0, 0, "rl_population_size")) return rc;
     if (n_members) *n_members = a->M;
     if (lanes_per_member) *lanes_per_member = a->G;
+    return RL_OK;
+}
+
+int rl_population_maps(rl_agent *a, uint32_t m0, uint32_t n, int32_t *map_ids, size_t n_out) {
+    if (int rc = population_window(a, m0, n, "rl_population_maps")) return rc;
+    if (a->cfg.env.kind != RL_ENV_FROZEN_LAKE && a->cfg.env.kind != RL_ENV_FROZEN_LAKE_EDITED)
+        return fail(RL_E_STATE, "rl_population_maps: the population's env is not FrozenLake / FrozenLakeEdited "
+                                "(it has no map)");
+    if (!map_ids) return fail(RL_E_ARG, "rl_population_maps: map_ids is null");
+    if (n_out != n) return fail(RL_E_ARG, "rl_population_maps: n_out must be n = " + std::to_string(n));
+    for (uint32_t i = 0; i < n; ++i) map_ids[i] = a->pop_maps ? a->map_ids[m0 + i] : a->cfg.env.map8x8;
     return RL_OK;
 }
 
@@ -2457,7 +2575,7 @@ int rl_agent_occupancy(rl_agent *a, uint32_t *groups_per_cu, uint64_t *lds_bytes
     HIPC(hipSetDevice(a->device));
     agent_sync_params(a);   // the kernel choice depends on the Q representation (KParams::fq)
     int n = 0;
-    if (a->pop) HIPC(a->pop_fn(a->kp, a->pp, a->grid, a->block, a->smem, a->stream, &n));
+    if (a->pop) HIPC(population_launch(a, &n));
     else HIPC(a->fn(a->kp, a->grid, a->block, a->smem, a->stream, &n));
     *groups_per_cu = (uint32_t)n;
     *lds_bytes = a->smem;

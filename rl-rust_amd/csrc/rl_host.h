@@ -35,7 +35,9 @@ struct EnvHost {
     uint32_t dev_n_start() const { return rlamd::env_map_start(kenv) ? n_list : (uint32_t)cdf.size(); }
 };
 
-int build_env(const rl_env_config &c, EnvHost &e);
+// as_map: a built-in FrozenLake map (id 0 / 1) in the registered maps' form too
+// (ENV_FL_MAP / ENV_FLE_MAP, fixed_start 0)
+int build_env(const rl_env_config &c, EnvHost &e, bool as_map = false);
 int net_feature_table(const rl_env_config &c, const EnvHost &e, int input, std::vector<double> &feat, uint32_t &n_in);
 
 #pragma GCC visibility pop

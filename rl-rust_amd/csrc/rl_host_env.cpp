@@ -123,7 +123,7 @@ bool map_lookup(int32_t id, Grid &out, bool *wide = nullptr) {
 
 }  // namespace
 
-int build_env(const rl_env_config &c, EnvHost &e) {
+int build_env(const rl_env_config &c, EnvHost &e, bool as_map) {
     e = EnvHost();
     e.kind = c.kind;
     e.kenv = c.kind;
@@ -140,8 +140,10 @@ int build_env(const rl_env_config &c, EnvHost &e) {
         e.nrow = nrow;
         e.ncol = ncol;
         // a registered map runs the kernels with the start variant (rl_kparams.h), a
-        // built-in one exactly the instantiations it always ran
-        if (c.map8x8 >= 2) e.kenv = edited ? ENV_FLE_MAP : ENV_FL_MAP;
+        // built-in one exactly the instantiations it always ran — unless the caller asks
+        // for the map form (as_map: a population on the members' own maps, where ids 0 / 1
+        // are narrow maps with the fixed start 0)
+        if (c.map8x8 >= 2 || as_map) e.kenv = edited ? ENV_FLE_MAP : ENV_FL_MAP;
         if (wide) e.kenv = edited ? ENV_FLE_WIDE : ENV_FL_WIDE;   // rl_map_register_wide: the wide table
         e.S = (uint32_t)(nrow * ncol);
         e.A = 4;

@@ -215,6 +215,25 @@ struct PopParams {
 typedef hipError_t (*pop_launch_fn)(const KParams &p, const PopParams &pp, dim3 grid, dim3 block, size_t smem,
                                     hipStream_t stream, int *occ);
 
+// A population on maps of the members' own (rl.h rl_population_create_maps;
+// k_train_population_maps, rl_train_population_maps.hip): the third argument.  Block m
+// takes envs[m] in place of KParams::trans / start_cdf / n_start / fixed_start; members
+// on one map share its table and start list.  carve_n_start is the largest n_start of
+// the members: the LDS carve every block makes (rl_train_impl.h train_shared_body).
+struct MemberEnv {
+    const uint32_t *trans;
+    const double *start;   // the start list (start_list_bytes), null with a fixed start
+    uint32_t n_start;
+    int32_t fixed_start;
+};
+struct PopMapParams {
+    const MemberEnv *envs;     // [M]
+    uint32_t carve_n_start;
+    uint32_t pad;
+};
+typedef hipError_t (*pop_maps_launch_fn)(const KParams &p, const PopParams &pp, const PopMapParams &pm, dim3 grid,
+                                         dim3 block, size_t smem, hipStream_t stream, int *occ);
+
 // one entry per (env, agent, policy, selector, private) kernel instantiation
 // occ != nullptr: no launch; *occ = resident workgroups per CU of the kernel
 // the launch would pick (hipOccupancyMaxActiveBlocksPerMultiprocessor)
@@ -232,6 +251,9 @@ train_launch_fn lookup_train(int env, int agent, int policy, int sel, int algo, 
 // the population kernel of a one-step (env, policy, selector, algorithm); nullptr outside
 // the supported slice (rl_train_population.hip)
 pop_launch_fn lookup_population(int env, int policy, int sel, int algo);
+// ... and of a population on the members' own maps: env one of ENV_FL_MAP / ENV_FLE_MAP /
+// ENV_FL_WIDE / ENV_FLE_WIDE (rl_train_population_maps.hip)
+pop_maps_launch_fn lookup_population_maps(int env, int policy, int sel, int algo);
 size_t shared_smem_bytes(int env, int agent, int policy, int sel, int algo, uint32_t S, uint32_t A,
                          uint32_t n_start, uint32_t nthr, uint32_t trc_kb, int fq, int ucb_pack);
 size_t private_smem_bytes(int env, int agent, int policy, int sel, uint32_t S, uint32_t A, uint32_t n_start);

@@ -511,10 +511,15 @@ constexpr bool fix_possible() {
 // POP: the block is member blockIdx.x of a population (rl_train_population.hip): p
 // holds that member's bases and scalars and pop_row is its stats row; the block is
 // the only writer of its tables, so it writes them back itself instead of emitting a
-// merge delta.
+// merge delta.  A population whose members run maps of their own
+// (rl_train_population_maps.hip) passes carve_n_start, the largest n_start over the
+// members: every block then carves the same LDS (the host sizes it once) while the
+// member's own p.n_start drives its start list's copy and search.
+constexpr uint32_t CARVE_OWN = 0xffffffffu;   // carve_n_start: the block's own p.n_start
 template <int ENV, int AGENT, int POLICY, int SEL, int ALGO, bool INSTR, bool FQ, int SLIP = -1, int SWEEP = -1,
           bool PACK = false, int RS = -1, int EPI = -1, bool POP = false>
-__device__ __forceinline__ void train_shared_body(const KParams &p, unsigned long long *pop_row = nullptr) {
+__device__ __forceinline__ void train_shared_body(const KParams &p, unsigned long long *pop_row = nullptr,
+                                                  uint32_t carve_n_start = CARVE_OWN) {
     using E = EnvDev<ENV>;
     constexpr int A = E::A;
     constexpr int P = POLICY == RL_POLICY_DOUBLE ? 2 : 1;
@@ -530,7 +535,9 @@ __device__ __forceinline__ void train_shared_body(const KParams &p, unsigned lon
     const uint32_t tid = threadIdx.x, nthr = blockDim.x;
     constexpr bool PAIRS = TRACES && !SPEC;            // layout_sparse_traces (rl_kparams.h)
     constexpr bool QSH = qsh_layout(FQ ? 1 : 0, UCB ? 1 : 0, P, ALGO);
-    const SmemLayout lay = smem_layout(ENV, P, UCB ? (SPEC ? 2 : 1) : 0, TRACES ? (PAIRS ? 2 : 1) : 0, S, A, p.n_start,
+    uint32_t carve_ns = p.n_start;
+    if constexpr (POP) carve_ns = carve_n_start == CARVE_OWN ? p.n_start : carve_n_start;
+    const SmemLayout lay = smem_layout(ENV, P, UCB ? (SPEC ? 2 : 1) : 0, TRACES ? (PAIRS ? 2 : 1) : 0, S, A, carve_ns,
                                        nthr, p.trc_kb, FQ ? 1 : 0, p.ucb_pack, QSH ? 1 : 0);
     unsigned long long *Q = (unsigned long long *)(smem + lay.q);
     double *QD = (double *)(smem + lay.qd);              // QSH: f64 images of Q's words

@@ -176,6 +176,8 @@ SIGNATURES = {
     "rl_agent_get_weights_lanes": (C.c_int, [_V, C.c_uint32, C.c_uint32, _V, C.c_size_t]),
     "rl_agent_trace_items": (C.c_int, [_V, _P(C.c_uint64)]),
     "rl_population_create": (C.c_int, [_P(AgentConfig), _P(MemberConfig), C.c_uint32, _P(_V)]),
+    "rl_population_create_maps": (C.c_int, [_P(AgentConfig), _P(MemberConfig), _P(C.c_int32), C.c_uint32, _P(_V)]),
+    "rl_population_maps": (C.c_int, [_V, C.c_uint32, C.c_uint32, _V, C.c_size_t]),
     "rl_population_size": (C.c_int, [_V, _P(C.c_uint32), _P(C.c_uint32)]),
     "rl_population_get_q": (C.c_int, [_V, C.c_uint32, C.c_uint32, _V, C.c_size_t]),
     "rl_population_get_q_raw": (C.c_int, [_V, C.c_uint32, C.c_uint32, _V, C.c_size_t]),
@@ -727,9 +729,13 @@ class Population:
     """M independent shared-Q agents in one launch (rl.h rl_population_create): member
     m is the Agent of member_params(base, members[m]) with n_lanes = group_size = G.
     base_params: default_params(...) with group_size = G (n_lanes is set to M * G);
-    members: dicts overriding MEMBER_KEYS."""
+    members: dicts overriding MEMBER_KEYS.
+    maps: one FrozenLake / FrozenLakeEdited map per member (rl_population_create_maps),
+    each a map id or a list of rows; rows are registered through register_map, in the
+    wide table format when `wide` is true or, left None, when base_params' own map8x8
+    is a wide id."""
 
-    def __init__(self, base_params, members):
+    def __init__(self, base_params, members, maps=None, wide=None):
         members = list(members)
         self.M, self.G = len(members), base_params["group_size"]
         self.p = dict(base_params, n_lanes=self.M * self.G)
@@ -737,7 +743,17 @@ class Population:
         self.cfg = agent_config(self.p)
         self._mc = member_configs(self.p, members)
         h = C.c_void_p()
-        check(lib().rl_population_create(C.byref(self.cfg), self._mc, self.M, C.byref(h)))
+        if maps is None:
+            check(lib().rl_population_create(C.byref(self.cfg), self._mc, self.M, C.byref(h)))
+        else:
+            maps = list(maps)
+            if len(maps) != self.M:
+                raise ValueError("maps needs one entry per member: %d for %d members" % (len(maps), self.M))
+            if wide is None and any(not isinstance(x, (int, np.integer)) for x in maps):
+                wide = map_is_wide(self.p["map8x8"])
+            ids = [int(x) if isinstance(x, (int, np.integer)) else register_map(x, wide=bool(wide)) for x in maps]
+            self._ids = (C.c_int32 * max(self.M, 1))(*ids)
+            check(lib().rl_population_create_maps(C.byref(self.cfg), self._mc, self._ids, self.M, C.byref(h)))
         self.h = h
         S, A, P = C.c_uint32(), C.c_uint32(), C.c_uint32()
         check(lib().rl_agent_dims(self.h, C.byref(S), C.byref(A), C.byref(P)))
@@ -759,6 +775,13 @@ class Population:
 
     def _window(self, m0, n):
         return m0, (self.M - m0 if n is None else n)
+
+    def maps(self, m0=0, n=None):
+        """[member] map ids (rl_population_maps)"""
+        m0, n = self._window(m0, n)
+        out = np.zeros(n, np.int32)
+        check(lib().rl_population_maps(self.h, m0, n, out.ctypes.data, out.size))
+        return out
 
     def run(self, n_launches):
         check(lib().rl_agent_run(self.h, n_launches))

@@ -20,6 +20,16 @@ clock around it; the library's HIP-event time of the train kernels alone
 (rl_agent_set_timing) comes from one more window of the same length per form.
 Prints one JSON document; --out writes it to a file as well.  Needs a GPU: there is
 no fallback.
+
+--maps times what a map of the member's own costs (rl_population_create_maps), the
+same way:
+  (a) the map population with every member on a registered copy of the built-in 8x8
+  (b) the built-in population of the same members (rl_population_create, map8x8 = 1):
+      the same work, so a / b is the cost of the map path
+  (c) the same members as lone map agents on their own streams
+and adds (d), one window series of a map population over M distinct random 8x8 lakes
+(--random-seed; one 'S' and one 'G' each, a fifth of the other cells holes).  Before
+timing, (a)'s member tables are checked equal to (b)'s and (c)'s.
 """
 import argparse
 import json
@@ -42,8 +52,10 @@ def _steps(h):
 class PopulationRun:
     name = "a_population"
 
-    def __init__(self, base, members):
-        self.pop = rlamd.Population(base, members)
+    def __init__(self, base, members, maps=None, name=None):
+        self.pop = rlamd.Population(base, members, maps=maps)
+        if name:
+            self.name = name
 
     def round(self, n):
         self.pop.run(n)
@@ -62,10 +74,10 @@ class PopulationRun:
 class LoneRun:
     """M lone agents; serial: wait for each agent before the next starts"""
 
-    def __init__(self, agents, serial):
+    def __init__(self, agents, serial, name=None):
         self.agents = agents
         self.serial = serial
-        self.name = "b_serial" if serial else "b_streams"
+        self.name = name or ("b_serial" if serial else "b_streams")
 
     def round(self, n):
         for a in self.agents:
@@ -133,6 +145,75 @@ def event_window(run, n):
     return dict(train_kernel_event_ms=ms, train_kernels=cnt, ms_per_train_kernel=ms / max(cnt, 1))
 
 
+def random_lake(rng, n=8, holes=0.2):
+    """n x n rows: 'S' and 'G' on two distinct random cells, `holes` of the rest 'H'"""
+    cells = np.where(rng.random(n * n) < holes, "H", "F")
+    s, g = rng.choice(n * n, size=2, replace=False)
+    cells[s], cells[g] = "S", "G"
+    return ["".join(cells[r * n:(r + 1) * n]) for r in range(n)]
+
+
+def measure(runs, args):
+    """warm-up, window lengths for at least --seconds, then the alternated repeats"""
+    n = {}
+    for r in runs:
+        r.round(2)
+        w = window(r, 4)
+        n[r.name] = max(4, int(np.ceil(4 * args.seconds / w["seconds"] * 1.1)))
+    reps = []
+    for i in range(args.repeats):
+        reps.append({r.name: window(r, n[r.name]) for r in runs})
+    rates = {k: [rep[k]["env_steps_per_s"] for rep in reps] for k in reps[0]}
+    return reps, rates
+
+
+def spread(v):
+    return dict(median=float(np.median(v)), min=min(v), max=max(v))
+
+
+def main_maps(args):
+    M, G = args.members, args.group
+    base = rlamd.default_params(env="frozen_lake", map8x8=1, algo="qlearning", group_size=G, n_lanes=G,
+                                sync_every=args.sync)
+    members = [dict(seed=0x5EED + m, lane_offset=m * G) for m in range(M)]
+    copy = rlamd.register_map(rlamd.map_info(1))
+    a = PopulationRun(base, members, maps=[copy] * M, name="a_map_population")
+    b = PopulationRun(base, members, name="b_builtin_population")
+    agents = [rlamd.Agent(dict(a.pop.members[m], n_lanes=G, group_size=G, map8x8=copy)) for m in range(M)]
+    a.round(2)
+    b.round(2)
+    raw = a.pop.q_raw()
+    if not np.array_equal(raw, b.pop.q_raw()):
+        raise SystemExit("the map population's tables differ from the built-in population's")
+    for m, ag in enumerate(agents):
+        ag.run(2)
+        if not np.array_equal(raw[m], ag.q_raw()):
+            raise SystemExit(f"member {m}: the map population's table differs from the lone map agent's")
+    runs = [a, b, LoneRun(agents, serial=False, name="c_lone_map_agents")]
+    reps, rates = measure(runs, args)
+    rng = np.random.default_rng(args.random_seed)
+    lakes = [random_lake(rng) for _ in range(M)]
+    d = PopulationRun(base, members, maps=lakes, name="d_distinct_random_maps")
+    d_reps, d_rates = measure([d], args)
+    out = dict(
+        mode="maps", build_id=rlamd.build_id(), members=M, lanes_per_member=G, sync_every=args.sync,
+        q_repr=a.pop.q_repr(), occupancy=dict(a=a.pop.occupancy(), b=b.pop.occupancy(), d=d.pop.occupancy()),
+        tables_equal_before_timing=True, repeats=reps,
+        env_steps_per_s={k: spread(v) for k, v in rates.items()},
+        a_over_b=[x / y for x, y in zip(rates["a_map_population"], rates["b_builtin_population"])],
+        a_over_c=[x / y for x, y in zip(rates["a_map_population"], rates["c_lone_map_agents"])],
+        distinct_random_maps=dict(n_distinct=len(set(d.pop.maps().tolist())), random_seed=args.random_seed,
+                                  repeats=d_reps, env_steps_per_s=spread(d_rates[d.name])),
+    )
+    text = json.dumps(out, indent=1)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--members", type=int, default=256)
@@ -141,7 +222,11 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--seconds", type=float, default=1.0, help="least length of a timed window")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--maps", action="store_true", help="time the map population (rl_population_create_maps)")
+    ap.add_argument("--random-seed", type=int, default=2026, help="--maps: seed of the distinct random lakes")
     args = ap.parse_args()
+    if args.maps:
+        return main_maps(args)
     M, G = args.members, args.group
 
     base = rlamd.default_params(env="frozen_lake", map8x8=1, algo="qlearning", group_size=G, n_lanes=G,
